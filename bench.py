@@ -11,6 +11,19 @@ Launch: python bench.py --gpus N --steps K --warmup W
   N>1 is launched by the driver via torch.distributed.run (one rank per GPU,
   RCCL over xGMI); this script reads RANK/LOCAL_RANK/WORLD_SIZE from the env.
 
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print the result line. Anything further the benchmark grows
+(baselines, other configs, per-kernel figures) belongs behind --full.
+
+--dump-outputs DIR writes what the last timed step produced, from rank 0:
+  DIR/losses.npy         float32 (4,): the step's return value — per-frame
+                         mean mse, kld, cpc, align losses
+  DIR/params_sample.npy  float32 (<=2^20,): the model parameters the step
+                         left behind, a fixed seeded sample of the flattened
+                         parameter vector
+Inputs, weights and the sampling noise are seeded, so the same arguments give
+the same inputs run after run and two builds can be compared file for file.
+
 Prints ONE JSON line from rank 0.
 """
 from __future__ import annotations
@@ -47,6 +60,23 @@ def make_synthetic_batch(cfg, device, seed: int):
     return x.to(device)
 
 
+DUMP_PARAM_SAMPLE = 1 << 20   # elements; 4 MB as float32
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(out_dir: str, losses, model) -> None:
+    """Write the last timed step's results as float32 .npy files."""
+    os.makedirs(out_dir, exist_ok=True)
+    vals = torch.stack([v.detach().float().reshape(()) for v in losses])
+    np.save(os.path.join(out_dir, "losses.npy"), vals.cpu().numpy())
+    flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+    if flat.numel() > DUMP_PARAM_SAMPLE:
+        g = torch.Generator(device="cpu").manual_seed(DUMP_SAMPLE_SEED)
+        idx = torch.randint(0, flat.numel(), (DUMP_PARAM_SAMPLE,), generator=g)
+        flat = flat[idx.sort().values.to(flat.device)]
+    np.save(os.path.join(out_dir, "params_sample.npy"), flat.cpu().numpy())
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -66,7 +96,17 @@ def main():
                    help="NHWC activations/weights (MIOpen igemm is NHWC-native)")
     p.add_argument("--use_graphs", type=int, default=-1,
                    help="-1: auto (on for single-GPU CUDA)")
+    p.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR",
+                   default=None,
+                   help="after the timed steps, write the last step's losses "
+                        "and a seeded sample of the updated parameters to "
+                        "DIR/*.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement or check; the "
+                        "benchmark has none yet, so this equals a plain run")
     args = p.parse_args()
+    if args.dump_outputs is not None and args.steps < 1:
+        p.error("--dump-outputs needs at least one timed step")
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -141,7 +181,7 @@ def main():
         )
 
         def one_step():
-            stepper.step(x)
+            return stepper.step(x)
 
     else:
 
@@ -149,9 +189,8 @@ def main():
             model.zero_grad(set_to_none=False)
             if amp:
                 with torch.autocast("cuda", dtype=torch.bfloat16):
-                    model(x, 0, len(x) - 1)
-            else:
-                model(x, 0, len(x) - 1)
+                    return model(x, 0, len(x) - 1)
+            return model(x, 0, len(x) - 1)
 
     # warmup
     for _ in range(args.warmup):
@@ -162,8 +201,9 @@ def main():
     if use_cuda:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
     if use_cuda:
         torch.cuda.synchronize()
     if world > 1:
@@ -175,6 +215,9 @@ def main():
         t = torch.tensor([elapsed], device=device if use_cuda else None)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, last, model)
 
     global_batch = args.batch * world
     frames = global_batch * args.seq_len * args.steps

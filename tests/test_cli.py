@@ -119,6 +119,52 @@ def test_bench_contract_cpu(tmp_path):
     assert d["config"]["global_batch"] == 2
 
 
+def test_bench_dump_outputs_reproducible_cpu(tmp_path):
+    """--dump-outputs writes the last timed step's losses and a sample of the
+    updated parameters as float32 .npy; the same arguments give the same
+    inputs, so two runs agree file for file. --steps is the number of timed
+    steps, and --full is accepted. Pinned to the CPU path so the comparison
+    is exact on every machine."""
+    import numpy as np
+
+    env = os.environ.copy()
+    env["PYTHONPATH"] = ROOT
+    env["CUDA_VISIBLE_DEVICES"] = ""
+    env["HIP_VISIBLE_DEVICES"] = ""
+    dumps = []
+    for sub, extra in (("a", []), ("b", ["--full"])):
+        out = tmp_path / sub / "dump"
+        r = subprocess.run(
+            [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+             "--steps", "2", "--warmup", "0", "--batch", "2", "--seq_len", "4",
+             "--dump-outputs", str(out), *extra],
+            cwd=ROOT, env=env, capture_output=True, text=True, timeout=600,
+        )
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.strip().splitlines()
+                 if ln.startswith("{")]
+        assert len(lines) == 1, f"expected exactly one JSON line: {r.stdout}"
+        d = json.loads(lines[0])
+        assert d["steps"] == 2 and d["warmup"] == 0
+        assert d["n_gpus"] == 0 and d["dtype"] == "fp32"
+        assert d["ms_per_step"] > 0
+        frames = d["config"]["global_batch"] * d["config"]["seq_len"] * 2
+        assert d["value"] == pytest.approx(
+            frames / (d["ms_per_step"] * 2 / 1000.0), rel=1e-6)
+        assert sorted(p.name for p in out.iterdir()) == [
+            "losses.npy", "params_sample.npy"]
+        arrs = {p.name: np.load(p) for p in out.iterdir()}
+        assert arrs["losses.npy"].shape == (4,)
+        assert 0 < arrs["params_sample.npy"].size <= 1 << 20
+        for a in arrs.values():
+            assert a.dtype == np.float32 and np.isfinite(a).all()
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2**20
+        dumps.append(arrs)
+    for name in dumps[0]:
+        np.testing.assert_allclose(dumps[0][name], dumps[1][name],
+                                   rtol=1e-5, atol=1e-6, err_msg=name)
+
+
 def test_phase_timing_harness_cpu():
     """SURVEY §5.1 per-phase timing harness runs on CPU and covers all six
     phases."""
@@ -253,9 +299,13 @@ def test_bench_distributed_2rank_gloo_cpu():
     """The exact multi-rank path the driver launches for SCALE runs:
     torch.distributed.run -> bench.py with world=2 (gloo on CPU here, RCCL
     on GPU boxes) — init, DDPGradSync, barriers, MAX-over-ranks timing,
-    one JSON line from rank 0 with parallelism dp2."""
+    one JSON line from rank 0 with parallelism dp2. The ranks are pinned to
+    the CPU/gloo path so the test also runs on a machine with fewer GPUs than
+    ranks."""
     env = os.environ.copy()
     env["PYTHONPATH"] = ROOT
+    env["CUDA_VISIBLE_DEVICES"] = ""
+    env["HIP_VISIBLE_DEVICES"] = ""
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
@@ -277,9 +327,12 @@ def test_bench_distributed_2rank_gloo_cpu():
 def test_train_ddp_2rank_gloo_cpu(tmp_path):
     """train.py under torch.distributed.run with 2 CPU ranks (gloo): real
     setup_distributed + per-rank data seeds + DDPGradSync in the epoch loop;
-    rank 0 owns logging/checkpoints."""
+    rank 0 owns logging/checkpoints. The ranks are pinned to the CPU/gloo
+    path so the test also runs on a machine with fewer GPUs than ranks."""
     env = os.environ.copy()
     env["PYTHONPATH"] = ROOT
+    env["CUDA_VISIBLE_DEVICES"] = ""
+    env["HIP_VISIBLE_DEVICES"] = ""
     log_dir = tmp_path / "logs" / "run"
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
