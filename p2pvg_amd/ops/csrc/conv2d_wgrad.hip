@@ -7,8 +7,10 @@
 // (Ci,R,S,Co)-physical transposed-conv weight grad.
 //
 // GEMM view per (r,s): (B x A) = Y^T @ X_patch, reduced over all N*HO*WO
-// pixels — a huge-K GEMM, split over pixel slabs (grid.z) with fp32
-// atomicAdd into a workspace (deterministic mode: splitP=1).
+// pixels — a huge-K GEMM, split over pixel slabs (grid.z). Every slab STORES
+// its fp32 partial into its own workspace plane (no atomics, no pre-zeroing)
+// and a combine kernel sums the planes in a fixed order, so the result is
+// bitwise-deterministic at any split factor.
 //
 // Both operands are pixel-major in memory (NHWC), so global loads are
 // contiguous 16B channel runs and staging writes are single ds_write_b128s
@@ -273,6 +275,17 @@ __device__ __forceinline__ void wglds16(const __bf16* g, char* l) {
       (__attribute__((address_space(3))) void*)l, 16, 0, 0);
 }
 
+// per-(wave, call, lane) fixed image coordinates: 16B unit index scall ->
+// subtiled-image (pix, ch0); every glds-staged side shares the decode
+// (BT/16 via shift)
+__device__ __forceinline__ void glds_decode(int scall, int bt16_sh, int& pix,
+                                            int& ch0) {
+  const int sidx = scall >> 3;
+  const int inner = scall & 7;
+  pix = ((sidx >> bt16_sh) << 2) + (inner >> 1);
+  ch0 = ((sidx & ((1 << bt16_sh) - 1)) << 4) + ((inner & 1) << 3);
+}
+
 template <int BTB, int BTA>
 __global__ __launch_bounds__(THREADS) void conv2d_wgrad_glds_kernel(
     const __bf16* __restrict__ Y, const __bf16* __restrict__ X,
@@ -313,14 +326,6 @@ __global__ __launch_bounds__(THREADS) void conv2d_wgrad_glds_kernel(
   constexpr int XC = XBYTES / 4096;
   constexpr int G = YC + XC;
 
-  // per-(wave, call, lane) fixed image coordinates: 16B unit index s ->
-  // subtiled-image (pix, ch0); both sides share the decode (BT via shift)
-  auto decode = [&](int scall, int bt16_sh, int& pix, int& ch0) {
-    const int sidx = scall >> 3;
-    const int inner = scall & 7;
-    pix = ((sidx >> bt16_sh) << 2) + (inner >> 1);
-    ch0 = ((sidx & ((1 << bt16_sh) - 1)) << 4) + ((inner & 1) << 3);
-  };
   constexpr int ybt_sh = BTB == 128 ? 3 : 2;
   constexpr int xbt_sh = BTA == 128 ? 3 : 2;
 
@@ -330,7 +335,7 @@ __global__ __launch_bounds__(THREADS) void conv2d_wgrad_glds_kernel(
 #pragma unroll
     for (int i = 0; i < YC; ++i) {
       int pixl, ch0;
-      decode((wid * YC + i) * 64 + lane, ybt_sh, pixl, ch0);
+      glds_decode((wid * YC + i) * 64 + lane, ybt_sh, pixl, ch0);
       const int pix = p0 + pixl;
       const int n = pix >> howo_sh;
       const int rem = pix - (n << howo_sh);
@@ -343,7 +348,7 @@ __global__ __launch_bounds__(THREADS) void conv2d_wgrad_glds_kernel(
 #pragma unroll
     for (int i = 0; i < XC; ++i) {
       int pixl, ch0;
-      decode((wid * XC + i) * 64 + lane, xbt_sh, pixl, ch0);
+      glds_decode((wid * XC + i) * 64 + lane, xbt_sh, pixl, ch0);
       const int pix = p0 + pixl;
       const int n = pix >> howo_sh;
       const int rem = pix - (n << howo_sh);
@@ -488,116 +493,280 @@ __global__ __launch_bounds__(THREADS) void conv2d_wgrad_glds_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// Small-A wgrad (the first conv: A = nc = 1 or 3 input channels). The MFMA
-// kernels pay for a 64-wide A tile that is ~95% masked there — and that
-// conv's wgrad was 6.6% of the whole headline step. Here the ENTIRE dW
-// accumulator (B*R*S*A <= 2048 cells) lives in the block's registers
-// (<= 8 cells/thread) and plain VALU rank-1 updates accumulate over an
-// LDS-staged pixel tile. Slab stores + the serial combine keep it
-// deterministic like the MFMA paths.
+// Thin-channel wgrad (first encoder conv / last decoder ConvT: A = 1..3).
+// The taps are folded into the thin channel axis, so the whole weight
+// gradient is ONE GEMM and one pass over Y serves every tap:
+//   dW[b, q] = sum_pix Y[pix, b] * Xcol[pix, q],   q = (r*S + s)*A + a < 32
+//   Xcol[pix, q] = X[n, ho*ST-PAD+r, wo*ST-PAD+s, a]  (0 out of bounds)
+// q is the inner index of the (B,R,S,A) layout: the slab store is
+// slab[b*R*S*A + q].
+//
+// Y side: the glds 3-buffer pipeline of conv2d_wgrad_glds_kernel<64,.>.
+// Xcol side: 64 pixels x 32 columns per chunk = 256 slots of (pixel, 8
+// consecutive q), one per thread. The thread's eight (r,s,a) triples are
+// decoded once; per chunk it issues eight 2-byte buffer loads whose hardware
+// range check returns 0 for the out-of-bounds offset we hand to masked
+// taps, packs them and writes one 16-byte LDS store into the subtiled image.
+//
+// vmcnt accounting. The gathers are inline asm so the compiler neither
+// drains the glds queue for them nor reorders them; loads retire in order,
+// and every iteration issues, in this order,
+//   Xg(t+2) [TXG ops, always — a chunk past the end gathers zeros]
+//   Ys(t+3) [TYC ops, only if the chunk exists]
+// One counted wait per iteration, taken just before X(t+1) is written to
+// LDS, retires Ys(t+1) and Xg(t+1) and leaves what was issued after them
+// outstanding: [Ys(t+2)], Xg(t+2), [Ys(t+3)] = TXG + TYC*[..] + TYC*[..].
 
-constexpr int SPIX = 32;
+constexpr int TQ = 32;                 // padded tap*channel columns
+constexpr int TYBYTES = PCH * 64 * 2;  // Y image per chunk
+constexpr int TXBYTES = PCH * TQ * 2;  // Xcol image per chunk
+constexpr int TSLAB = TYBYTES + TXBYTES;
+constexpr int TYC = TYBYTES / 4096;    // glds calls per wave per chunk
+constexpr int TXG = 8;                 // gather loads per thread per chunk
 
-__global__ __launch_bounds__(THREADS) void conv2d_wgrad_smalla_kernel(
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+struct XRegs {
+  unsigned v[TXG];
+};
+
+// wait until at most N vector-memory ops are outstanding; naming the gather
+// registers read-write keeps every consumer of them behind the wait
+template <int N>
+__device__ __forceinline__ void thin_wait(XRegs& x) {
+  asm volatile("s_waitcnt vmcnt(%8)"
+               : "+v"(x.v[0]), "+v"(x.v[1]), "+v"(x.v[2]), "+v"(x.v[3]),
+                 "+v"(x.v[4]), "+v"(x.v[5]), "+v"(x.v[6]), "+v"(x.v[7])
+               : "n"(N)
+               : "memory");
+}
+
+// retire a chunk that has `later` chunks behind it: leave outstanding the
+// TXG gather ops and the Y stages of up to two later chunks that were issued
+// after it (see the accounting above). The three-way choice lives INSIDE
+// one statement: a branch in C++ lets the compiler copy the still-landing
+// gather registers on the way to the wait.
+__device__ __forceinline__ void thin_retire(int later, XRegs& x) {
+  static_assert(TXG + 2 * TYC == 12 && TXG + TYC == 10 && TXG == 8,
+                "wait constants below are spelled out");
+  asm volatile(
+      "s_cmp_ge_i32 %8, 2\n\t"
+      "s_cbranch_scc0 .Lthin_w1_%=\n\t"
+      "s_waitcnt vmcnt(12)\n\t"
+      "s_branch .Lthin_wd_%=\n"
+      ".Lthin_w1_%=:\n\t"
+      "s_cmp_eq_u32 %8, 1\n\t"
+      "s_cbranch_scc0 .Lthin_w0_%=\n\t"
+      "s_waitcnt vmcnt(10)\n\t"
+      "s_branch .Lthin_wd_%=\n"
+      ".Lthin_w0_%=:\n\t"
+      "s_waitcnt vmcnt(8)\n"
+      ".Lthin_wd_%=:"
+      : "+v"(x.v[0]), "+v"(x.v[1]), "+v"(x.v[2]), "+v"(x.v[3]),
+        "+v"(x.v[4]), "+v"(x.v[5]), "+v"(x.v[6]), "+v"(x.v[7])
+      : "s"(__builtin_amdgcn_readfirstlane(later))
+      : "memory", "scc");
+}
+
+__global__ __launch_bounds__(THREADS) void conv2d_wgrad_thin_kernel(
     const __bf16* __restrict__ Y, const __bf16* __restrict__ X,
     float* __restrict__ ws, int Nb, int HO, int WO, int B, int H, int W,
     int A, int R, int S, int STRIDE, int PAD, int p_per_slab, int yring,
-    int howo_sh, int wo_sh) {
-  __shared__ struct __align__(16) {
-    float g[SPIX][64 + 1];
-    float xv[SPIX][64];
-  } lds;
-  const int RSA = R * S * A;
-  const int E = B * RSA;
-  const int tid = threadIdx.x;
+    int howo_sh, int wo_sh, int xbytes) {
+  __shared__ __align__(16) char tlds[3 * TSLAB];
+
+  const int b0 = blockIdx.x * 64;
   const int p_begin = blockIdx.z * p_per_slab;
   const int p_total = Nb * HO * WO;
   const int p_end = min(p_begin + p_per_slab, p_total);
+  const int RSA = R * S * A;
+
+  const int tid = threadIdx.x;
+  const int wid = tid >> 6;
+  const int lane = tid & 63;
   const int HOp = HO + 2 * yring;
   const int WOp = WO + 2 * yring;
 
-  // this thread's dW cells: cell = c*THREADS + tid. Decode ONCE — the
-  // inner loop must be pure LDS-read + fma (a per-iteration cell/RSA
-  // divide serialized the first version). Cells beyond E alias (0,0);
-  // their accumulator is garbage but never stored.
-  float acc[12];
-  int bcell[12], jcell[12];
-  const int ncells = (E + THREADS - 1) / THREADS;
+  // wave w owns b rows [16w, 16w+16) x all 32 columns: 1 x 2 fragments
+  f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+
+  // raw buffer over X: an offset >= xbytes reads as 0
+  const unsigned long long xaddr = (unsigned long long)X;
+  const i32x4 xrsrc = {(int)(unsigned)xaddr, (int)((xaddr >> 32) & 0xffffu),
+                       xbytes, 0x00020000};
+  constexpr unsigned XOOB = 0x80000000u;
+
+  // this thread's Xcol slot: pixel tid/4 of the chunk, columns q0..q0+7
+  const int xpix = tid >> 2;
+  const int q0 = (tid & 3) * 8;
+  int xdh[TXG], xdw[TXG], xoff[TXG];
 #pragma unroll
-  for (int c = 0; c < 12; ++c) {
-    acc[c] = 0.f;
-    const int cell = c * THREADS + tid;
-    const int b = cell < E ? cell / RSA : 0;
-    bcell[c] = b;
-    jcell[c] = cell < E ? cell - b * RSA : 0;
+  for (int j = 0; j < TXG; ++j) {
+    const int q = q0 + j;
+    const int rs = q / A;
+    const int a = q - rs * A;
+    const int r = rs / S;
+    const int s = rs - r * S;
+    // a padding column never passes the row bound check
+    xdh[j] = q < RSA ? r - PAD : -(1 << 24);
+    xdw[j] = s - PAD;
+    xoff[j] = ((r - PAD) * W + (s - PAD)) * A + a;
+  }
+  const unsigned xlds =
+      (unsigned)(unsigned long long)tlds + TYBYTES + sub_off<TQ>(xpix, q0);
+
+  auto pix_decode = [&](int pix, int& n, int& ho, int& wo) {
+    n = pix >> howo_sh;
+    const int rem = pix - (n << howo_sh);
+    ho = rem >> wo_sh;
+    wo = rem - (ho << wo_sh);
+  };
+
+  // TXG range-checked 2-byte loads, always issued; !live gathers zeros
+  auto gather = [&](int p0, bool live, XRegs& x) {
+    int n, ho, wo;
+    pix_decode(p0 + xpix, n, ho, wo);
+    const int hi0 = ho * STRIDE;
+    const int wi0 = wo * STRIDE;
+    const int base = ((n * H + hi0) * W + wi0) * A;
+#pragma unroll
+    for (int j = 0; j < TXG; ++j) {
+      const bool ok = live && (unsigned)(hi0 + xdh[j]) < (unsigned)H &&
+                      (unsigned)(wi0 + xdw[j]) < (unsigned)W;
+      const unsigned voff = ok ? (unsigned)(base + xoff[j]) * 2u : XOOB;
+      asm volatile("buffer_load_ushort %0, %1, %2, 0 offen"
+                   : "=v"(x.v[j])
+                   : "v"(voff), "s"(xrsrc)
+                   : "memory");
+    }
+  };
+
+  auto write_x = [&](int buf, const XRegs& x) {
+    const u32x4 w = {x.v[0] | (x.v[1] << 16), x.v[2] | (x.v[3] << 16),
+                     x.v[4] | (x.v[5] << 16), x.v[6] | (x.v[7] << 16)};
+    asm volatile("ds_write_b128 %0, %1" ::"v"(xlds + buf * TSLAB), "v"(w)
+                 : "memory");
+  };
+
+  auto stage_y = [&](int p0, int buf) {
+    char* yimg = tlds + buf * TSLAB;
+#pragma unroll
+    for (int i = 0; i < TYC; ++i) {
+      int pixl, ch0, n, ho, wo;
+      glds_decode((wid * TYC + i) * 64 + lane, 2, pixl, ch0);
+      pix_decode(p0 + pixl, n, ho, wo);
+      const long yoff =
+          (((long)n * HOp + ho + yring) * WOp + wo + yring) * B + b0 + ch0;
+      wglds16(Y + yoff, yimg + (wid * TYC + i) * 1024);
+    }
+  };
+
+  auto mfma_image = [&](int buf) {
+    const char* yimg = tlds + buf * TSLAB;
+    const char* ximg = yimg + TYBYTES;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const int pe = kk * 32 + (lane >> 4) * 8;
+      u16x4 alo, ahi, blo[2], bhi[2];
+      tr16_issue(yimg, wid * 16 + (lane & 15), pe, lane, 4, alo, ahi);
+#pragma unroll
+      for (int f = 0; f < 2; ++f)
+        tr16_issue(ximg, f * 16 + (lane & 15), pe, lane, TQ / 16, blo[f],
+                   bhi[f]);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      const bf16x8 a_frag = tr16_combine(alo, ahi);
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            a_frag, tr16_combine(blo[j], bhi[j]), acc[j], 0, 0, 0);
+    }
+  };
+
+  const int nfull = (p_end - p_begin) / PCH;
+  const int tail = (p_end - p_begin) - nfull * PCH;
+
+  // retire chunk c: its Y glds and its gather have landed after this
+  auto retire = [&](int c, XRegs& x) { thin_retire(nfull - 1 - c, x); };
+
+  XRegs xa, xb;
+  // iteration t: `cur` holds Xg(t+1) in flight, `nxt` receives Xg(t+2)
+  auto step = [&](int t, XRegs& cur, XRegs& nxt) {
+    const int buf = t % 3;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // X(t) is in LDS
+    wbarrier_mem();
+    mfma_image(buf);
+    wbarrier_mem();
+    gather(p_begin + (t + 2) * PCH, t + 2 < nfull, nxt);
+    __builtin_amdgcn_sched_barrier(0);
+    if (t + 3 < nfull) stage_y(p_begin + (t + 3) * PCH, buf);
+    __builtin_amdgcn_sched_barrier(0);
+    retire(t + 1, cur);
+    write_x((t + 1) % 3, cur);
+  };
+
+  if (nfull > 0) {
+    gather(p_begin, true, xb);
+    __builtin_amdgcn_sched_barrier(0);
+    stage_y(p_begin, 0);
+    if (nfull > 1) stage_y(p_begin + PCH, 1);
+    __builtin_amdgcn_sched_barrier(0);
+    gather(p_begin + PCH, nfull > 1, xa);
+    __builtin_amdgcn_sched_barrier(0);
+    if (nfull > 2) stage_y(p_begin + 2 * PCH, 2);
+    __builtin_amdgcn_sched_barrier(0);
+    retire(0, xb);
+    write_x(0, xb);
+    for (int t = 0; t < nfull; t += 2) {
+      step(t, xa, xb);
+      if (t + 1 >= nfull) break;
+      step(t + 1, xb, xa);
+    }
+    // the last (zero) gathers are still landing in xa/xb
+    thin_wait<0>(xa);
+    thin_wait<0>(xb);
   }
 
-  for (int p0 = p_begin; p0 < p_end; p0 += SPIX) {
-    // stage gout rows (SPIX x B) and the RSA gathers (SPIX x RSA)
-    {
-      const int r = tid >> 3;            // 0..31 pixel
-      const int c0 = (tid & 7) * 8;      // 8 channels per thread
-      const int pix = p0 + r;
-      if (pix < p_end) {
-        long yoff = (long)pix * B;
-        if (yring > 0) {
-          const int n = pix >> howo_sh;
-          const int rem = pix - (n << howo_sh);
-          const int ho = rem >> wo_sh;
-          const int wo = rem - (ho << wo_sh);
-          yoff = (((long)n * HOp + ho + yring) * WOp + wo + yring) * B;
-        }
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-          lds.g[r][c0 + c] = c0 + c < B ? (float)Y[yoff + c0 + c] : 0.f;
-      } else {
-#pragma unroll
-        for (int c = 0; c < 8; ++c) lds.g[r][c0 + c] = 0.f;
-      }
-    }
-    {
-      // xv: each of the 256 threads stages up to ceil(SPIX*RSA/256) values
-      const int nval = SPIX * RSA;
-      for (int i = tid; i < SPIX * 64; i += THREADS) {
-        const int r = i >> 6;            // pixel
-        const int j = i & 63;            // rsa index
-        float v = 0.f;
-        const int pix = p0 + r;
-        if (j < RSA && pix < p_end) {
-          const int n = pix >> howo_sh;
-          const int rem = pix - (n << howo_sh);
-          const int ho = rem >> wo_sh;
-          const int wo = rem - (ho << wo_sh);
-          const int rs = j / A;
-          const int a = j - rs * A;
-          const int rr = rs / S;
-          const int ss = rs - rr * S;
-          const int hi = ho * STRIDE - PAD + rr;
-          const int wi = wo * STRIDE - PAD + ss;
-          if (hi >= 0 && hi < H && wi >= 0 && wi < W)
-            v = (float)X[((long)n * H * W + (long)hi * W + wi) * A + a];
-        }
-        lds.xv[r][j] = v;
-        (void)nval;
-      }
-    }
+  if (tail > 0) {
+    // ragged last chunk: masked register staging into buffer 0
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();
-    for (int r = 0; r < SPIX; ++r) {
+    const int p0 = p_begin + nfull * PCH;
+    gather(p0, xpix < tail, xa);
+    constexpr int SLY = (PCH * 64 / 8) / THREADS;
 #pragma unroll
-      for (int c = 0; c < 12; ++c) {
-        acc[c] = fmaf(lds.g[r][bcell[c]], lds.xv[r][jcell[c]], acc[c]);
+    for (int it = 0; it < SLY; ++it) {
+      const int slot = it * THREADS + tid;
+      const int pixl = slot >> 3;
+      const int ch0 = (slot & 7) * 8;
+      bf16x8 vy = {};
+      if (pixl < tail) {
+        int n, ho, wo;
+        pix_decode(p0 + pixl, n, ho, wo);
+        vy = *reinterpret_cast<const bf16x8*>(
+            Y + (((long)n * HOp + ho + yring) * WOp + wo + yring) * B + b0 +
+            ch0);
       }
+      *reinterpret_cast<bf16x8*>(tlds + sub_off<64>(pixl, ch0)) = vy;
     }
-    (void)ncells;
+    thin_wait<0>(xa);
+    write_x(0, xa);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();
+    mfma_image(0);
   }
 
-  float* slab = ws + (long)blockIdx.z * E;
+  float* slab = ws + (long)blockIdx.z * B * RSA;
 #pragma unroll
-  for (int c = 0; c < 12; ++c) {
-    if (c >= ncells) break;
-    const int cell = c * THREADS + tid;
-    if (cell < E) slab[cell] = acc[c];
+  for (int j = 0; j < 2; ++j) {
+    const int q = j * 16 + (lane & 15);
+    if (q >= RSA) continue;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int b = b0 + wid * 16 + (lane >> 4) * 4 + v;
+      slab[(long)b * RSA + q] = acc[j][v];
+    }
   }
 }
 
@@ -613,6 +782,38 @@ __global__ __launch_bounds__(256) void wgrad_combine_kernel(
   }
 }
 
+// Two-level form of the combine for the thin path, whose many slabs
+// (sp ~ 1024) over few elements would make the single serial walk visible:
+// CGR fixed groups of ceil(sp/CGR) consecutive slabs are summed serially in
+// parallel, then the CGR group partials serially (cf. fold_rows_kernel).
+// The association order is a function of sp alone.
+constexpr int CGR = 32;  // slab groups
+constexpr int CEL = 8;   // elements per block
+__global__ __launch_bounds__(CGR * CEL) void wgrad_combine2_kernel(
+    const float* __restrict__ ws, float* __restrict__ out, int sp, int E,
+    int accumulate) {
+  __shared__ float part[CGR][CEL];
+  const int el = threadIdx.x % CEL;
+  const int g = threadIdx.x / CEL;
+  const int e = blockIdx.x * CEL + el;
+  const int zs = (sp + CGR - 1) / CGR;
+  const int z0 = g * zs;
+  const int z1 = min(sp, z0 + zs);
+  float t = 0.f;
+  if (e < E) {
+#pragma unroll 8
+    for (int z = z0; z < z1; ++z) t += ws[(long)z * E + e];
+  }
+  part[g][el] = t;
+  __syncthreads();
+  if (g == 0 && e < E) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < CGR; ++k) s += part[k][el];
+    out[e] = accumulate ? out[e] + s : s;
+  }
+}
+
 }  // namespace
 
 // Y: channels_last (N,B,HO,WO) bf16; X: channels_last (N,A,H,W) bf16.
@@ -621,10 +822,12 @@ __global__ __launch_bounds__(256) void wgrad_combine_kernel(
 // weight's channels_last .grad): the combine ACCUMULATES into it in place
 // and returns it — this is how the framework skips autograd's per-use grad
 // accumulation adds entirely (the ~29 uses per weight per step land here).
+// thin: -1 picks the thin-channel path when the geometry allows it, 0 never
+// takes it, 1 requires it (raises otherwise).
 torch::Tensor conv2d_nhwc_wgrad(torch::Tensor Y, torch::Tensor X, long R,
                                 long S, long stride, long pad, long splitp,
                                 c10::optional<torch::Tensor> acc, long yring,
-                                c10::optional<torch::Tensor> X2) {
+                                c10::optional<torch::Tensor> X2, long thin) {
   TORCH_CHECK(Y.is_cuda() && Y.scalar_type() == torch::kBFloat16 &&
                   Y.is_contiguous(at::MemoryFormat::ChannelsLast),
               "Y must be bf16 channels_last GPU");
@@ -653,9 +856,23 @@ torch::Tensor conv2d_nhwc_wgrad(torch::Tensor Y, torch::Tensor X, long R,
   const int BTA = (A >= 128 && A % 128 == 0) ? 128 : 64;
   const int bt = ceil_div(B, BTB), at = ceil_div(A, BTA);
   const int p_total = Nb * HO * WO;
+  const bool pow2 = ((HO * WO) & (HO * WO - 1)) == 0 && (WO & (WO - 1)) == 0;
+
+  // thin-channel path: all taps folded into <= 32 GEMM columns, any pad/yring
+  const bool thin_ok = !X2.has_value() && R * S * A <= TQ && B % 64 == 0 &&
+                       (stride == 1 || stride == 2) && pow2 && HO > 0 &&
+                       WO > 0 && pad >= 0 && yring >= 0 &&
+                       X.numel() * 2 < (1L << 31);
+  TORCH_CHECK(thin != 1 || thin_ok,
+              "wgrad: thin path required but the geometry is not eligible");
+  const bool use_thin = thin_ok && thin != 0;
+
   int sp = (int)splitp;
   if (sp <= 0) {
-    sp = std::max(1, 1024 / std::max(1, bt * at * (int)R * (int)S));
+    // thin: 36 KB of LDS per block -> 4 blocks per CU resident; ~1024 blocks
+    // keep every CU's HBM queue full (one block holds only 24 KB in flight)
+    sp = use_thin ? std::max(1, 1024 / (B / 64))
+                  : std::max(1, 1024 / std::max(1, bt * at * (int)R * (int)S));
     sp = std::min(sp, ceil_div(p_total, PCH));
   }
   const int p_per_slab =
@@ -669,57 +886,23 @@ torch::Tensor conv2d_nhwc_wgrad(torch::Tensor Y, torch::Tensor X, long R,
   dim3 grid(bt * at, (int)(R * S), sp);
   auto stream = at::cuda::getCurrentCUDAStream();
 
-  const bool pow2 = ((HO * WO) & (HO * WO - 1)) == 0 && (WO & (WO - 1)) == 0;
   const bool use_glds = pad == 0 && pow2 && HO > 0 && WO > 0 &&
                         B % BTB == 0 && A % BTA == 0 &&
                         (X2.has_value() || p_total >= 4 * PCH);
   TORCH_CHECK(!X2.has_value() || use_glds,
               "wgrad: dual-X requires the glds-eligible geometry");
-  // DISABLED: three iterations (divide decode, hoisted cells, shift-only
-  // decode) all measured net headline losses vs the masked MFMA tile —
-  // the cost model is wrong somewhere (per-thread scalar LDS read volume
-  // is the prime suspect); docs/ROADMAP.md records the attempts. Flip to
-  // re-enable for tuning.
-  const bool use_smalla = false && !X2.has_value() && A <= 8 && B <= 64 &&
-                          R * S * A <= 64 &&
-                          (long)B * R * S * A <= 3072 && pow2;
-  if (use_smalla) {
-    // tiny-A path: register-resident dW, VALU rank-1 updates
-    const long E = (long)B * R * S * A;
-    int spa = (int)std::min<long>(448, ceil_div(p_total, SPIX));
-    const int pps = ceil_div(ceil_div(p_total, spa), SPIX) * SPIX;
-    spa = ceil_div(p_total, pps);
-    auto wsa = torch::empty({spa, B, (long)R, (long)S, A},
-                            Y.options().dtype(torch::kFloat32));
-    dim3 g(1, 1, spa);
+  if (use_thin) {
     int howo_sh = 0, wo_sh = 0;
     while ((1 << howo_sh) < HO * WO) ++howo_sh;
     while ((1 << wo_sh) < WO) ++wo_sh;
-    hipLaunchKernelGGL(conv2d_wgrad_smalla_kernel, g, dim3(THREADS), 0,
-                       stream, reinterpret_cast<const __bf16*>(Y.data_ptr()),
+    hipLaunchKernelGGL(conv2d_wgrad_thin_kernel, dim3(B / 64, 1, sp),
+                       dim3(THREADS), 0, stream,
+                       reinterpret_cast<const __bf16*>(Y.data_ptr()),
                        reinterpret_cast<const __bf16*>(X.data_ptr()),
-                       wsa.data_ptr<float>(), Nb, HO, WO, B, H, W, A, (int)R,
-                       (int)S, (int)stride, (int)pad, pps, (int)yring,
-                       howo_sh, wo_sh);
-    torch::Tensor out;
-    int accumulate = 0;
-    if (acc.has_value()) {
-      out = acc.value();
-      TORCH_CHECK(out.scalar_type() == torch::kFloat32 &&
-                      out.is_non_overlapping_and_dense() && out.numel() == E,
-                  "wgrad acc: need dense fp32 tensor with B*R*S*A elements");
-      accumulate = 1;
-    } else {
-      out = torch::empty({B, (long)R, (long)S, A},
-                         Y.options().dtype(torch::kFloat32));
-    }
-    hipLaunchKernelGGL(wgrad_combine_kernel,
-                       dim3((int)std::min<long>(64, (E + 255) / 256)),
-                       dim3(256), 0, stream, wsa.data_ptr<float>(),
-                       out.data_ptr<float>(), spa, E, accumulate);
-    return out;
-  }
-  if (use_glds) {
+                       ws.data_ptr<float>(), Nb, HO, WO, B, H, W, A, (int)R,
+                       (int)S, (int)stride, (int)pad, p_per_slab, (int)yring,
+                       howo_sh, wo_sh, (int)(X.numel() * 2));
+  } else if (use_glds) {
     // PAD==0 means every X gather is in-bounds (padded operand or genuine
     // valid conv): glds 3-buffer pipeline, shift-only pixel decode
     int howo_sh = 0, wo_sh = 0;
@@ -778,6 +961,12 @@ torch::Tensor conv2d_nhwc_wgrad(torch::Tensor Y, torch::Tensor X, long R,
     if (sp == 1) return ws[0];
     out = torch::empty({B, (long)R, (long)S, A},
                        Y.options().dtype(torch::kFloat32));
+  }
+  if (use_thin) {
+    hipLaunchKernelGGL(wgrad_combine2_kernel, dim3(ceil_div((int)E, CEL)),
+                       dim3(CGR * CEL), 0, stream, ws.data_ptr<float>(),
+                       out.data_ptr<float>(), sp, (int)E, accumulate);
+    return out;
   }
   const int cgrid = (int)std::min<long>(2048, (E + 255) / 256);
   hipLaunchKernelGGL(wgrad_combine_kernel, dim3(cgrid), dim3(256), 0, stream,
