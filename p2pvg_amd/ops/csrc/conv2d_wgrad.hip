@@ -770,6 +770,254 @@ __global__ __launch_bounds__(THREADS) void conv2d_wgrad_thin_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Single-pass 3x3 wgrad: all nine taps from one staged read of Y and X.
+// (stride 1, PAD == 0 over a zero-ringed X, B and A multiples of 64.)
+//
+// One block owns a 64(b) x 64(a) weight tile for ALL nine taps (grid.x walks
+// the tiles, grid.z the pixel slabs). The pixel axis is cut into 32-column
+// strips of the output map; a chunk is two output rows of one strip (64
+// pixels, two 32-pixel MFMA K-steps), so every map width >= 32 runs the same
+// code: 32 -> one strip, 64 -> two, 128 -> four.
+//
+// X side: each input row of the strip is staged ONCE as three column-shifted
+// [32 pix][64 ch] subtiled images (global_load_lds takes a per-lane source
+// address, so image s simply reads X[hi][wo0 + pix + s]). Tap (r,s) of
+// output row ho is then the plain aligned tr16 read of image s of input row
+// ho + r. The row images live in a ring of TP_NR slots: a chunk needs four
+// input rows, of which two were staged by the chunk before it, so advancing
+// a chunk stages two rows (6 images) and one 64-pixel Y image: 8 KB + 24 KB
+// against 9 x 16 KB for the per-tap kernel. The ring restarts (four rows)
+// at the first chunk of a slab and of every (image, strip) segment.
+//
+// Ring size: when chunk k is staged, chunk k-2 has not been computed (4
+// rows) and chunk k-1 is in flight; at most one of k-1, k is a restart:
+// 4 + 2 + 4 = 10 slots, handed out by a running counter.
+//
+// Pipeline: Y in 3 buffers, one raw barrier per chunk. At the top of
+// iteration t only stage(t+1) was issued after stage(t), and a stage is at
+// least TP_G glds calls per wave, so vmcnt(TP_G) retires chunk t (it waits
+// for a little more than needed when t+1 is a restart).
+//
+// Waves: 2 x 2 over the tile, each 32(b) x 32(a) x 9 taps = 36 fragments
+// (144 accumulator registers). Per K-step a wave reads 2 Y fragments once
+// and 18 X fragments: 40 transpose reads for 36 MFMAs.
+
+constexpr int TPW = 32;                      // strip width, pixels per row image
+constexpr int TP_IMG = TPW * 64 * 2;         // one shifted row image, 4 KB
+constexpr int TP_ROW = 3 * TP_IMG;           // the three shifts of one row
+constexpr int TP_NR = 10;                    // row ring slots
+constexpr int TP_Y = PCH * 64 * 2;           // Y image of one chunk, 8 KB
+constexpr int TP_LDS = TP_NR * TP_ROW + 3 * TP_Y;  // 144 KB
+constexpr int TP_G = 2 * 3 + 2;              // glds calls/wave, steady chunk
+
+template <int OFF>
+__device__ __forceinline__ void tr16_issue_at(unsigned addr, u16x4& lo,
+                                              u16x4& hi) {
+  // the pair of tr16_issue, as immediates off a per-lane base: second half of
+  // the 8-pixel run is the next pixel-group row of the 64-channel image
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
+               : "=v"(lo)
+               : "v"(addr), "n"(OFF));
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
+               : "=v"(hi)
+               : "v"(addr), "n"(OFF + 4 * 128));
+}
+
+// wait until at most N LDS reads are outstanding; naming the fragment
+// registers read-write keeps their consumers behind the wait
+template <int N>
+__device__ __forceinline__ void taps_wait(u16x4& a, u16x4& b, u16x4& c,
+                                          u16x4& d) {
+  asm volatile("s_waitcnt lgkmcnt(%4)"
+               : "+v"(a), "+v"(b), "+v"(c), "+v"(d)
+               : "n"(N)
+               : "memory");
+}
+
+__global__ __launch_bounds__(THREADS) void conv2d_wgrad_taps_kernel(
+    const __bf16* __restrict__ Y, const __bf16* __restrict__ X,
+    const __bf16* __restrict__ X2, float* __restrict__ ws, int HO, int WO,
+    int B, int H, int W, int A, int A1, int yring, int nchunks, int cps,
+    int seg_sh, int strip_sh) {
+  extern __shared__ __align__(16) char plds[];
+  char* const ybufs = plds + TP_NR * TP_ROW;
+
+  const int at_blocks = A >> 6;
+  const int b0 = (blockIdx.x / at_blocks) * 64;
+  const int a0 = (blockIdx.x % at_blocks) * 64;
+  const int c_begin = blockIdx.z * cps;
+  const int nch = min(c_begin + cps, nchunks) - c_begin;
+
+  const int tid = threadIdx.x;
+  const int wid = tid >> 6;
+  const int lane = tid & 63;
+  const int wm = (wid >> 1) * 32;
+  const int wn = (wid & 1) * 32;
+  const int HOp = HO + 2 * yring;
+  const int WOp = WO + 2 * yring;
+
+  // dual-X: the 64-wide a-tile lies wholly in one source (A1 % 64 == 0)
+  const bool second = X2 != nullptr && a0 >= A1;
+  const __bf16* xsrc = second ? X2 + (a0 - A1) : X + a0;
+  const int as = X2 == nullptr ? A : (second ? A - A1 : A1);
+  const __bf16* ysrc = Y + b0;
+
+  // per-lane staging offsets (elements), fixed for the whole kernel
+  int xl_off[3], yl_off[2];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int q = wid * 3 + i;  // 1 KB unit of the 12 KB row: image q/4
+    int pixl, ch0;
+    glds_decode((q & 3) * 64 + lane, 2, pixl, ch0);
+    xl_off[i] = (pixl + (q >> 2)) * as + ch0;
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    int pixl, ch0;
+    glds_decode((wid * 2 + i) * 64 + lane, 2, pixl, ch0);
+    yl_off[i] = ((pixl >> 5) * WOp + (pixl & (TPW - 1))) * B + ch0;
+  }
+
+  const int seg_mask = (1 << seg_sh) - 1;
+  const int strip_mask = (1 << strip_sh) - 1;
+  auto restart = [&](int c) { return c == c_begin || (c & seg_mask) == 0; };
+
+  int sctr = 0;  // ring slot the next staged row goes to
+  auto stage = [&](int c, int ybuf) {
+    const int seg = c >> seg_sh;
+    const int n = seg >> strip_sh;
+    const int wo0 = (seg & strip_mask) * TPW;
+    const int ho0 = (c & seg_mask) * 2;
+    const bool fresh = restart(c);
+    const int hi0 = fresh ? ho0 : ho0 + 2;
+    const int nrows = fresh ? 4 : 2;
+    for (int j = 0; j < nrows; ++j) {
+      const __bf16* rb = xsrc + ((long)(n * H + hi0 + j) * W + wo0) * as;
+      char* l = plds + sctr * TP_ROW + wid * 3 * 1024;
+      sctr = sctr + 1 == TP_NR ? 0 : sctr + 1;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) wglds16(rb + xl_off[i], l + i * 1024);
+    }
+    const __bf16* yb =
+        ysrc + (((long)n * HOp + ho0 + yring) * WOp + wo0 + yring) * B;
+    char* l = ybufs + ybuf * TP_Y + wid * 2 * 1024;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) wglds16(yb + yl_off[i], l + i * 1024);
+  };
+
+  f32x4 acc[9][2][2];
+#pragma unroll
+  for (int tp = 0; tp < 9; ++tp)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc[tp][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // per-lane tr16 base inside a 64-channel image: pixel run (lane>>4)*8,
+  // column lane&15 of channel subtile w/16 (fragment f adds 128 B)
+  const unsigned lane_rd = (unsigned)((lane >> 4) * 2 * 4 * 128 + (lane & 15) * 8);
+  const unsigned yrd = (unsigned)(unsigned long long)ybufs + lane_rd +
+                       (unsigned)((wm >> 4) * 128);
+  const unsigned xrd = (unsigned)(unsigned long long)plds + lane_rd +
+                       (unsigned)((wn >> 4) * 128);
+
+  int cctr = 0;  // ring slot of the first row the next restart chunk reads
+  auto compute = [&](int c, int ybuf) {
+    const bool fresh = restart(c);
+    int slot = fresh ? cctr : (cctr >= 2 ? cctr - 2 : cctr - 2 + TP_NR);
+    cctr += fresh ? 4 : 2;
+    cctr = cctr >= TP_NR ? cctr - TP_NR : cctr;
+    unsigned rowa[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      rowa[j] = xrd + (unsigned)(slot * TP_ROW);
+      slot = slot + 1 == TP_NR ? 0 : slot + 1;
+    }
+    const unsigned ya = yrd + (unsigned)(ybuf * TP_Y);
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      u16x4 ylo[2], yhi[2], xlo[2][2], xhi[2][2];
+      // Y image: K-step kk is pixels kk*32.. = pixel-group rows kk*8..
+      if (kk == 0) {
+        tr16_issue_at<0>(ya, ylo[0], yhi[0]);
+        tr16_issue_at<128>(ya, ylo[1], yhi[1]);
+      } else {
+        tr16_issue_at<8 * 512>(ya, ylo[0], yhi[0]);
+        tr16_issue_at<8 * 512 + 128>(ya, ylo[1], yhi[1]);
+      }
+      tr16_issue_at<0>(rowa[kk], xlo[0][0], xhi[0][0]);
+      tr16_issue_at<128>(rowa[kk], xlo[0][1], xhi[0][1]);
+#pragma unroll
+      for (int tp = 0; tp < 9; ++tp) {
+        const int cur = tp & 1, nxt = cur ^ 1;
+        if (tp < 8) {
+          // images of tap tp+1: row kk + r, shift s
+          const unsigned ra = rowa[kk + (tp + 1) / 3];
+          switch ((tp + 1) % 3) {
+            case 0:
+              tr16_issue_at<0>(ra, xlo[nxt][0], xhi[nxt][0]);
+              tr16_issue_at<128>(ra, xlo[nxt][1], xhi[nxt][1]);
+              break;
+            case 1:
+              tr16_issue_at<TP_IMG>(ra, xlo[nxt][0], xhi[nxt][0]);
+              tr16_issue_at<TP_IMG + 128>(ra, xlo[nxt][1], xhi[nxt][1]);
+              break;
+            default:
+              tr16_issue_at<2 * TP_IMG>(ra, xlo[nxt][0], xhi[nxt][0]);
+              tr16_issue_at<2 * TP_IMG + 128>(ra, xlo[nxt][1], xhi[nxt][1]);
+              break;
+          }
+          if (tp == 0) taps_wait<4>(ylo[0], yhi[0], ylo[1], yhi[1]);
+          taps_wait<4>(xlo[cur][0], xhi[cur][0], xlo[cur][1], xhi[cur][1]);
+        } else {
+          taps_wait<0>(xlo[cur][0], xhi[cur][0], xlo[cur][1], xhi[cur][1]);
+        }
+        bf16x8 yf[2], xf[2];
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+          yf[f] = tr16_combine(ylo[f], yhi[f]);
+          xf[f] = tr16_combine(xlo[cur][f], xhi[cur][f]);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            acc[tp][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                yf[i], xf[j], acc[tp][i][j], 0, 0, 0);
+      }
+    }
+  };
+
+  if (nch > 0) stage(c_begin, 0);
+  if (nch > 1) stage(c_begin + 1, 1);
+  int ybuf = 0;
+  for (int t = 0; t < nch; ++t) {
+    if (t + 1 < nch) wwaitcnt_vm<TP_G>();
+    else wwaitcnt_vm<0>();
+    wbarrier_mem();
+    // buffer (t+2)%3 and the slots it takes were last read by chunk t-1
+    if (t + 2 < nch) stage(c_begin + t + 2, ybuf >= 1 ? ybuf - 1 : 2);
+    compute(c_begin + t, ybuf);
+    ybuf = ybuf == 2 ? 0 : ybuf + 1;
+  }
+
+  float* slab = ws + (long)blockIdx.z * B * 9 * A;
+#pragma unroll
+  for (int tp = 0; tp < 9; ++tp)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int a = a0 + wn + j * 16 + (lane & 15);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int b = b0 + wm + i * 16 + (lane >> 4) * 4 + v;
+          slab[((long)b * 9 + tp) * A + a] = acc[tp][i][j][v];
+        }
+    }
+}
+
 // out[e] (+)= sum over slabs ws[z][e] — serial over z (deterministic).
 __global__ __launch_bounds__(256) void wgrad_combine_kernel(
     const float* __restrict__ ws, float* __restrict__ out, int sp, long E,
@@ -814,6 +1062,38 @@ __global__ __launch_bounds__(CGR * CEL) void wgrad_combine2_kernel(
   }
 }
 
+// (B, A, width) classes auto sends to the all-taps kernel: the 32-wide ones
+// measured in profiles/prof_wgrad_b512.txt (B 64..128, A 64..256). There the
+// result is bitwise the per-tap path's, so training results do not move.
+// Wider maps are faster still but sum in strip order: a different fp32
+// rounding of ~1e-6, which a training step amplifies (see ROADMAP); they
+// stay on the per-tap path.
+bool taps_auto(int B, int A, int WO) {
+  return B <= 128 && A <= 256 && WO == 32;
+}
+
+// fixed-order combine of the 3x3 slab planes (or accumulate into `acc`)
+torch::Tensor wgrad_finish(torch::Tensor ws, c10::optional<torch::Tensor> acc,
+                           int sp, int B, int A, long E, hipStream_t stream) {
+  torch::Tensor out;
+  int accumulate = 0;
+  if (acc.has_value()) {
+    out = acc.value();
+    TORCH_CHECK(out.scalar_type() == torch::kFloat32 &&
+                    out.is_non_overlapping_and_dense() && out.numel() == E,
+                "wgrad acc: need dense fp32 tensor with B*R*S*A elements");
+    accumulate = 1;
+  } else {
+    if (sp == 1) return ws[0];
+    out = torch::empty({B, 3, 3, A}, ws.options());
+  }
+  const int cgrid = (int)std::min<long>(2048, (E + 255) / 256);
+  hipLaunchKernelGGL(wgrad_combine_kernel, dim3(cgrid), dim3(256), 0, stream,
+                     ws.data_ptr<float>(), out.data_ptr<float>(), sp, E,
+                     accumulate);
+  return out;
+}
+
 }  // namespace
 
 // Y: channels_last (N,B,HO,WO) bf16; X: channels_last (N,A,H,W) bf16.
@@ -823,11 +1103,13 @@ __global__ __launch_bounds__(CGR * CEL) void wgrad_combine2_kernel(
 // and returns it — this is how the framework skips autograd's per-use grad
 // accumulation adds entirely (the ~29 uses per weight per step land here).
 // thin: -1 picks the thin-channel path when the geometry allows it, 0 never
-// takes it, 1 requires it (raises otherwise).
+// takes it, 1 requires it (raises otherwise). taps: the same three values for
+// the single-pass all-taps 3x3 kernel.
 torch::Tensor conv2d_nhwc_wgrad(torch::Tensor Y, torch::Tensor X, long R,
                                 long S, long stride, long pad, long splitp,
                                 c10::optional<torch::Tensor> acc, long yring,
-                                c10::optional<torch::Tensor> X2, long thin) {
+                                c10::optional<torch::Tensor> X2, long thin,
+                                long taps) {
   TORCH_CHECK(Y.is_cuda() && Y.scalar_type() == torch::kBFloat16 &&
                   Y.is_contiguous(at::MemoryFormat::ChannelsLast),
               "Y must be bf16 channels_last GPU");
@@ -867,6 +1149,17 @@ torch::Tensor conv2d_nhwc_wgrad(torch::Tensor Y, torch::Tensor X, long R,
               "wgrad: thin path required but the geometry is not eligible");
   const bool use_thin = thin_ok && thin != 0;
 
+  // single-pass all-taps path: 3x3 stride 1 over a zero-ringed X, 64-aligned
+  // channels (each X part), 32-column strips and two-row chunks
+  const bool taps_ok =
+      !use_thin && R == 3 && S == 3 && stride == 1 && pad == 0 && yring >= 0 &&
+      B % 64 == 0 && A1 % 64 == 0 && A % 64 == 0 && pow2 && WO >= TPW &&
+      HO >= 4 && H >= HO + 2 && W >= WO + 2;
+  TORCH_CHECK(taps != 1 || taps_ok,
+              "wgrad: taps path required but the geometry is not eligible");
+  const bool use_taps =
+      taps_ok && (taps == 1 || (taps != 0 && taps_auto(B, A, WO)));
+
   int sp = (int)splitp;
   if (sp <= 0) {
     // thin: 36 KB of LDS per block -> 4 blocks per CU resident; ~1024 blocks
@@ -878,6 +1171,36 @@ torch::Tensor conv2d_nhwc_wgrad(torch::Tensor Y, torch::Tensor X, long R,
   const int p_per_slab =
       ceil_div(ceil_div(p_total, sp), PCH) * PCH;  // chunk-aligned
   sp = ceil_div(p_total, p_per_slab);
+
+  if (use_taps) {
+    // the slabs are those of the per-tap path (same sp rule, same 64-pixel
+    // chunk alignment), and so is the combine. On a 32-wide map a K-step is
+    // the same 32 pixels in the same order there and here, so the result is
+    // bitwise the per-tap path's; on wider maps the strip order differs.
+    int seg_sh = 0, strip_sh = 0;
+    while ((2 << seg_sh) < HO) ++seg_sh;          // chunks per (image, strip)
+    while ((TPW << strip_sh) < WO) ++strip_sh;    // strips per row
+    const int tiles = (B / 64) * (A / 64);
+    auto tws = torch::empty({sp, B, 3, 3, A},
+                            Y.options().dtype(torch::kFloat32));
+    static bool cfg = false;
+    if (!cfg) {
+      (void)hipFuncSetAttribute((const void*)&conv2d_wgrad_taps_kernel,
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                TP_LDS);
+      cfg = true;
+    }
+    auto tstream = at::cuda::getCurrentCUDAStream();
+    hipLaunchKernelGGL(
+        conv2d_wgrad_taps_kernel, dim3(tiles, 1, sp), dim3(THREADS), TP_LDS,
+        tstream, reinterpret_cast<const __bf16*>(Y.data_ptr()),
+        reinterpret_cast<const __bf16*>(X.data_ptr()),
+        X2.has_value() ? reinterpret_cast<const __bf16*>(X2->data_ptr())
+                       : nullptr,
+        tws.data_ptr<float>(), HO, WO, B, H, W, A, A1, (int)yring,
+        p_total / PCH, p_per_slab / PCH, seg_sh, strip_sh);
+    return wgrad_finish(tws, acc, sp, B, A, E, tstream);
+  }
 
   // per-slab planes, written by stores — never zeroed
   auto ws = torch::empty({sp, B, (long)R, (long)S, A},

@@ -82,7 +82,8 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor x, torch::Tensor dy,
 torch::Tensor conv2d_nhwc_wgrad(torch::Tensor Y, torch::Tensor X, long R,
                                 long S, long stride, long pad, long splitp,
                                 c10::optional<torch::Tensor> acc, long yring,
-                                c10::optional<torch::Tensor> X2, long thin);
+                                c10::optional<torch::Tensor> X2, long thin,
+                                long taps);
 std::vector<torch::Tensor> maxpool2x2_fwd(torch::Tensor in, long ri, long ro);
 torch::Tensor maxpool2x2_bwd(torch::Tensor gout, torch::Tensor idx, long H,
                              long W, long ri, long ro);
@@ -147,12 +148,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_nhwc_wgrad", &conv2d_nhwc_wgrad,
         "NHWC wgrad, split-K over pixel slabs (gfx950 MFMA, deterministic); "
         "acc: fp32 dense (B,R,S,A)-layout tensor to accumulate into; "
-        "thin: -1 auto, 0 never, 1 require the thin-channel path",
+        "thin: -1 auto, 0 never, 1 require the thin-channel path; "
+        "taps: the same for the single-pass all-taps 3x3 path",
         pybind11::arg("Y"), pybind11::arg("X"), pybind11::arg("R"),
         pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"),
         pybind11::arg("splitp") = 0, pybind11::arg("acc") = c10::nullopt,
         pybind11::arg("yring") = 0, pybind11::arg("X2") = c10::nullopt,
-        pybind11::arg("thin") = -1);
+        pybind11::arg("thin") = -1, pybind11::arg("taps") = -1);
   m.def("maxpool2x2_fwd", &maxpool2x2_fwd, "NHWC 2x2/s2 maxpool fwd (gfx950)",
         pybind11::arg("in"), pybind11::arg("ri") = 0, pybind11::arg("ro") = 0);
   m.def("maxpool2x2_bwd", &maxpool2x2_bwd, "NHWC 2x2/s2 maxpool bwd (gfx950)",
