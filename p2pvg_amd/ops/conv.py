@@ -266,8 +266,9 @@ class Conv2dNHWCFn(torch.autograd.Function):
             oh = ow = oy = 0
             if out_ring:
                 H = x.shape[2] - 2 * in_ring
-                ho = (H + 2 * pad - k) // stride + 1
-                oh = ow = ho + 2 * out_ring
+                W = x.shape[3] - 2 * in_ring
+                oh = (H + 2 * pad - k) // stride + 1 + 2 * out_ring
+                ow = (W + 2 * pad - k) // stride + 1 + 2 * out_ring
                 oy = out_ring
             out, stats = ext.conv2d_nhwc_fwd(
                 x, wf, b32, stride, pad - in_ring, act, want_stats,
@@ -379,8 +380,9 @@ class CatConv2dFn(torch.autograd.Function):
         oh = ow = oy = 0
         if out_ring:
             H = x1.shape[2] - 2 * ring
-            ho = (H + 2 * pad - k) // stride + 1
-            oh = ow = ho + 2 * out_ring
+            W = x1.shape[3] - 2 * ring
+            oh = (H + 2 * pad - k) // stride + 1 + 2 * out_ring
+            ow = (W + 2 * pad - k) // stride + 1 + 2 * out_ring
             oy = out_ring
         out, stats = ext.conv2d_glds_fwd(x1, wf, None, stride, act,
                                          want_stats, oh, ow, oy, oy, x2)
@@ -483,11 +485,13 @@ class ConvT2dNHWCFn(torch.autograd.Function):
             assert in_ring in (0, k - 1 - pad), "convT in_ring mismatch"
             wt = w_fwd if w_fwd is not None else \
                 w.flip(2, 3).transpose(0, 1).contiguous(memory_format=CL)  # (Co,Ci,k,k)
-            ho = h + k - 1 - 2 * pad
-            oh = ho + 2 * out_ring if out_ring else 0
+            oh = ow = 0
+            if out_ring:
+                oh = h + k - 1 - 2 * pad + 2 * out_ring
+                ow = wdt + k - 1 - 2 * pad + 2 * out_ring
             out, stats = ext.conv2d_nhwc_fwd(x, wt, b32, 1,
                                              k - 1 - pad - in_ring, act,
-                                             want_stats, oh, oh,
+                                             want_stats, oh, ow,
                                              out_ring, out_ring)
         else:
             oh = (h - 1) * stride - 2 * pad + k

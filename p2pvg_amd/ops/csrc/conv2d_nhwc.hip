@@ -80,7 +80,9 @@ struct ConvArgs {
   int smap[4][4];
   int padh[4], padw[4];
   int oy0[4], ox0[4], oys;
-  float* stats;         // optional (2,K) sum/sumsq accumulation, or null
+  float* stats;         // optional (nz*mblocks*2, 2, K) sum/sumsq bucket rows,
+                        // one per (parity, block, wave-pair), each written
+                        // once by plain stores (never zeroed); or null
 };
 
 // KSIZE: compact kernel size (taps per axis). FRAC: parity mode. RSCLIN:
@@ -445,8 +447,11 @@ void check_nhwc_bf16(const torch::Tensor& t, const char* name) {
 
 // in: channels_last (N,C,H,W) bf16; w: channels_last (K,C,R,S) bf16;
 // bias: (K) fp32 optional. act: 0 none, 1 leaky(0.2), 2 tanh, 3 sigmoid.
-// stats: optional (2,K) fp32 ZEROED buffer accumulating sum/sumsq of the
-// activated output per channel (for fused BatchNorm statistics).
+// Returns (out, stats). With want_stats, stats is a (mblocks*2, 2, K) fp32
+// tensor allocated here: one bucket row per (block, wave-pair) holding that
+// bucket's per-channel sum and sum of squares of the activated output, each
+// entry written once by a store. The fused BatchNorm's finalize adds the rows
+// up in a fixed order; summing over dim 0 gives the (2,K) totals.
 std::vector<torch::Tensor> conv2d_nhwc_fwd(torch::Tensor in, torch::Tensor w,
                                             c10::optional<torch::Tensor> bias,
                                             long stride, long pad, long act,
