@@ -63,6 +63,8 @@ class Config:
                                       #   unconditionally every 50 iters, a full DtoH sync)
     deterministic: bool = False
     num_workers: int = 1
+    mnist_synth: str = "loader"       # loader | device  (device = host trajectory plan +
+                                      #   on-device render, no DataLoader; mnist only)
 
     # -- runtime-derived (never serialized as live objects) --
     optimizer: Any = field(default=None, repr=False, compare=False)

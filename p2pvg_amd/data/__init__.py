@@ -6,7 +6,9 @@ the target device, truncated to a per-batch dynamic length drawn by the
 dataset. MI355X-native differences: pinned host memory + non_blocking HtoD
 (the reference does a blocking `.cuda()` per batch, data_utils.py:100,116),
 device is configurable (CPU works), and under DDP each rank seeds its workers
-with a rank offset so shards differ.
+with a rank offset so shards differ. `mnist_synth="device"` swaps the
+MovingMNIST DataLoader for a host trajectory planner plus an on-device render
+(`get_device_mnist_generator`); the frames are bit-identical to the dataset's.
 """
 from __future__ import annotations
 
@@ -139,9 +141,49 @@ def get_h36m_generator(loader: DataLoader, device, dynamic_length: bool = True) 
             yield (pose_2d, pose_3d, camera_view)
 
 
+def get_device_mnist_generator(data, cfg, device, train: bool = True,
+                               dynamic_length: bool = True, rank: int = 0) -> Iterator:
+    """MovingMNIST batches without a DataLoader (`--mnist_synth device`).
+
+    Per batch the host only plans trajectories (`data.plan_batch`, the
+    dataset's own random draws from a generator-owned RandomState) and ships
+    the ~120 KB plan; the frames are rendered on `device` from the 32px sprite
+    bank kept there (ops.moving_mnist_render: HIP kernel on GPU, slice-adds on
+    CPU). Yields (seq_len, B, 1, S, S) fp32 with the strides of the CUDA
+    branch of `get_generator`: each x[i] is a channels_last frame.
+    """
+    import numpy as np
+
+    from ..ops import moving_mnist_render
+
+    digits = data.digits.contiguous().to(device)
+    rng = np.random.RandomState(
+        (torch.initial_seed() + rank * 7919 + (0 if train else 1)) % (2**31))
+    B, S, T = cfg.batch_size, data.image_size, data.max_seq_len
+
+    def _gen():
+        while True:
+            idx, pos = data.plan_batch(B, rng)
+            seq_len = T
+            if dynamic_length:
+                seq_len = int(rng.randint(T - 2 * data.delta_len, T + 1))
+            x = moving_mnist_render(digits, idx, pos[:seq_len], S)
+            yield x.view(seq_len, B, S, S, 1).permute(0, 1, 4, 2, 3)
+
+    return _gen()
+
+
 def get_data_generator(data, train: bool = True, dynamic_length: bool = True, opt=None, rank: int = 0):
     cfg = opt
     device = torch.device(cfg.resolved_device() if hasattr(cfg, "resolved_device") else "cpu")
+    synth = getattr(cfg, "mnist_synth", "loader")
+    if synth not in ("loader", "device"):
+        raise ValueError(f"mnist_synth must be 'loader' or 'device', got {synth!r}")
+    if synth == "device":
+        if cfg.dataset != "mnist":
+            raise ValueError(
+                f"mnist_synth='device' needs dataset='mnist', got {cfg.dataset!r}")
+        return get_device_mnist_generator(data, cfg, device, train, dynamic_length, rank)
     if cfg.dataset == "h36m":
         bs = cfg.batch_size if train else 10
         loader = _make_loader(data, bs, cfg, rank)

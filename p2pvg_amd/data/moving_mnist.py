@@ -177,3 +177,67 @@ class DynamicLengthMovingMNIST(torch.utils.data.Dataset):
 
         x.clamp_(max=1.0)
         return x
+
+    def plan_batch(self, batch_size: int, rng: np.random.RandomState):
+        """Trajectories of one batch without rendering a pixel.
+
+        Performs exactly the draws `__getitem__` performs, in the same order
+        (sample after sample, digit after digit: index, sx, sy, dx, dy, then
+        the per-timestep bounce re-draws), but from `rng` instead of the
+        global numpy state. Returns CPU tensors `idx` (B, D) int32 and `pos`
+        (T, B, D, 2) int32 holding (sy, sx) — the plan
+        `ops.moving_mnist_render` turns into frames bit-identical to stacking
+        `batch_size` `__getitem__` results drawn from the same stream.
+        """
+        T, D = self.max_seq_len, self.num_digits
+        lim = self.image_size - 32
+        det = self.deterministic
+        randint = rng.randint
+        idx = np.empty((batch_size, D), dtype=np.int32)
+        pos = np.empty((T, batch_size, D, 2), dtype=np.int32)
+        for b in range(batch_size):
+            for d in range(D):
+                idx[b, d] = randint(self.N)
+                sx = int(randint(lim))
+                sy = int(randint(lim))
+                dx = int(randint(-4, 5))
+                dy = int(randint(-4, 5))
+                ys, xs = [0] * T, [0] * T
+                for t in range(T):
+                    if sy < 0:
+                        sy = 0
+                        if det:
+                            dy = -dy
+                        else:
+                            dy = int(randint(1, 5))
+                            dx = int(randint(-4, 5))
+                    elif sy >= lim:
+                        sy = lim - 1
+                        if det:
+                            dy = -dy
+                        else:
+                            dy = int(randint(-4, 0))
+                            dx = int(randint(-4, 5))
+
+                    if sx < 0:
+                        sx = 0
+                        if det:
+                            dx = -dx
+                        else:
+                            dx = int(randint(1, 5))
+                            dy = int(randint(-4, 5))
+                    elif sx >= lim:
+                        sx = lim - 1
+                        if det:
+                            dx = -dx
+                        else:
+                            dx = int(randint(-4, 0))
+                            dy = int(randint(-4, 5))
+
+                    ys[t] = sy
+                    xs[t] = sx
+                    sy += dy
+                    sx += dx
+                pos[:, b, d, 0] = ys
+                pos[:, b, d, 1] = xs
+        return torch.from_numpy(idx), torch.from_numpy(pos)

@@ -132,9 +132,23 @@ def fused_adam_available() -> bool:
     return ext is not None and hasattr(ext, "multi_tensor_adam")
 
 
+# ---------------------------------------------------------------------------
+# MovingMNIST synthesis from a host trajectory plan
+# ---------------------------------------------------------------------------
+
+def moving_mnist_render(digits: torch.Tensor, idx: torch.Tensor,
+                        pos: torch.Tensor, image_size: int) -> torch.Tensor:
+    """Render a `DynamicLengthMovingMNIST.plan_batch` plan on digits.device:
+    HIP kernel on GPU, the dataset's slice-adds on CPU (ops/mnist_synth.py)."""
+    from .mnist_synth import moving_mnist_render as _render
+
+    return _render(digits, idx, pos, image_size)
+
+
 __all__ = [
     "lstm_cell",
     "gaussian_kl",
+    "moving_mnist_render",
     "backend_mode",
     "hip_available",
     "fused_adam_available",

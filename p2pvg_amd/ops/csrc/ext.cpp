@@ -92,6 +92,8 @@ torch::Tensor upsample2x_bwd(torch::Tensor gout, long ri, long ro);
 torch::Tensor channel_sum_nhwc(torch::Tensor x,
                                c10::optional<torch::Tensor> acc);
 torch::Tensor sqdiff_sum(torch::Tensor a, torch::Tensor b);
+torch::Tensor moving_mnist_render(torch::Tensor digits, torch::Tensor idx,
+                                  torch::Tensor pos, long S);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
@@ -171,4 +173,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gaussian_kl_fwd", &gaussian_kl_fwd, "fused gaussian KL fwd (gfx950)");
   m.def("gaussian_kl_bwd", &gaussian_kl_bwd, "fused gaussian KL bwd (gfx950)");
   m.def("sqdiff_sum", &sqdiff_sum, "fused sum((a-b)^2), bf16/f32 in fp32 out");
+  m.def("moving_mnist_render", &moving_mnist_render,
+        "MovingMNIST frames from a host-validated trajectory plan (gfx950); "
+        "digits (N,32,32) f32, idx (B,D) i32, pos (L,B,D,2) i32 -> "
+        "(L,B,1,S,S) f32",
+        pybind11::arg("digits"), pybind11::arg("idx"), pybind11::arg("pos"),
+        pybind11::arg("S"));
 }
