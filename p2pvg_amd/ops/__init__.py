@@ -145,10 +145,23 @@ def moving_mnist_render(digits: torch.Tensor, idx: torch.Tensor,
     return _render(digits, idx, pos, image_size)
 
 
+# ---------------------------------------------------------------------------
+# Per-frame SSIM + MSE for evaluation
+# ---------------------------------------------------------------------------
+
+# (ssim, mse) per image pair of (..., C, H, W) tensors, fp32, shaped like the
+# leading dimensions: one fused HIP pass on GPU, utils.metrics on CPU. Bound
+# here, at import: the submodule has the op's name, and a later first import
+# of it would rebind `ops.frame_metrics` to the module.
+from .frame_metrics import frame_metrics, frame_metrics_backend  # noqa: E402
+
+
 __all__ = [
     "lstm_cell",
     "gaussian_kl",
     "moving_mnist_render",
+    "frame_metrics",
+    "frame_metrics_backend",
     "backend_mode",
     "hip_available",
     "fused_adam_available",

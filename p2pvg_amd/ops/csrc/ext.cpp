@@ -94,6 +94,8 @@ torch::Tensor channel_sum_nhwc(torch::Tensor x,
 torch::Tensor sqdiff_sum(torch::Tensor a, torch::Tensor b);
 torch::Tensor moving_mnist_render(torch::Tensor digits, torch::Tensor idx,
                                   torch::Tensor pos, long S);
+std::vector<torch::Tensor> frame_metrics(torch::Tensor a, torch::Tensor b,
+                                         torch::Tensor win, double data_range);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
@@ -179,4 +181,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(L,B,1,S,S) f32",
         pybind11::arg("digits"), pybind11::arg("idx"), pybind11::arg("pos"),
         pybind11::arg("S"));
+  m.def("frame_metrics", &frame_metrics,
+        "fused per-image SSIM + MSE (gfx950, deterministic); a, b (M,C,H,W) "
+        "strided fp32/bf16/fp16, win = eleven fp32 window weights on the CPU "
+        "-> (ssim (M) f32, mse (M) f32)",
+        pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("win"),
+        pybind11::arg("data_range") = 1.0);
 }
