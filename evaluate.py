@@ -43,6 +43,10 @@ def main(argv=None) -> int:
     parser.add_argument("--device", type=str, default="auto")
     parser.add_argument("--dtype", type=str, default="fp32", choices=["fp32", "bf16"],
                         help="bf16 wraps generation in autocast (GPU only)")
+    parser.add_argument("--frame_cache", type=str, default="loader",
+                        choices=["loader", "device"],
+                        help="device: keep the decoded test frames on the device "
+                             "(bair only); always overrides the checkpoint's value")
     parser.add_argument("--out", type=str, default="eval.json")
     args = parser.parse_args(argv)
 
@@ -54,6 +58,7 @@ def main(argv=None) -> int:
               file=sys.stderr)
         return 2
     cfg.device = args.device
+    cfg.frame_cache = args.frame_cache
     if args.data_root is not None:
         cfg.data_root = args.data_root
     if args.batch_size is not None:

@@ -65,6 +65,8 @@ class Config:
     num_workers: int = 1
     mnist_synth: str = "loader"       # loader | device  (device = host trajectory plan +
                                       #   on-device render, no DataLoader; mnist only)
+    frame_cache: str = "loader"       # loader | device  (device = decoded uint8 frames kept on
+                                      #   the device, HIP batch gather, no DataLoader; bair only)
 
     # -- runtime-derived (never serialized as live objects) --
     optimizer: Any = field(default=None, repr=False, compare=False)

@@ -9,6 +9,9 @@ device is configurable (CPU works), and under DDP each rank seeds its workers
 with a rank offset so shards differ. `mnist_synth="device"` swaps the
 MovingMNIST DataLoader for a host trajectory planner plus an on-device render
 (`get_device_mnist_generator`); the frames are bit-identical to the dataset's.
+`frame_cache="device"` does the same for BAIR with the decoded frames kept on
+the device as uint8 and one gather kernel per batch
+(`get_device_bair_generator`).
 """
 from __future__ import annotations
 
@@ -173,9 +176,82 @@ def get_device_mnist_generator(data, cfg, device, train: bool = True,
     return _gen()
 
 
+UPLOAD_STAGE_BYTES = 64 << 20  # pinned staging buffer of the frame-bank upload
+
+
+def upload_frame_bank(pack, device) -> torch.Tensor:
+    """A `BairRobotPush.load_pack` array (memory-mapped or not) as a uint8
+    tensor on `device`. On a GPU the pack goes up once, in slices through one
+    pinned staging buffer of UPLOAD_STAGE_BYTES, after a check that it fits."""
+    import numpy as np
+
+    device = torch.device(device)
+    if device.type != "cuda":
+        return torch.from_numpy(np.array(pack))  # an in-memory, writable copy
+    free, _total = torch.cuda.mem_get_info(device)
+    if pack.nbytes > free:
+        raise ValueError(
+            f"the frame pack is {pack.nbytes / 2**30:.2f} GiB but only "
+            f"{free / 2**30:.2f} GiB of device memory is free on {device}: "
+            "frame_cache='device' keeps every decoded frame on the device")
+    bank = torch.empty(pack.shape, dtype=torch.uint8, device=device)
+    flat_dst = bank.view(-1)
+    flat_src = pack.reshape(-1)  # a view: load_pack arrays are C-contiguous
+    stage = torch.empty(min(UPLOAD_STAGE_BYTES, pack.nbytes), dtype=torch.uint8,
+                        pin_memory=True)
+    stage_np = stage.numpy()
+    for a in range(0, pack.nbytes, stage.numel()):
+        n = min(stage.numel(), pack.nbytes - a)
+        stage_np[:n] = flat_src[a:a + n]
+        flat_dst[a:a + n].copy_(stage[:n], non_blocking=True)
+        torch.cuda.current_stream(device).synchronize()  # stage is reused
+    return bank
+
+
+def get_device_bair_generator(data, cfg, device, train: bool = True,
+                              dynamic_length: bool = True, rank: int = 0) -> Iterator:
+    """BAIR batches without a DataLoader (`--frame_cache device`).
+
+    The split is decoded once (`data.load_pack`, cached on disk) and kept on
+    `device` as uint8; under DDP each rank holds the whole bank. Per batch the
+    host only draws the clip indices (`data.plan_batch`, the dataset's own
+    draws from a generator-owned RandomState) and ships those ~2 KB;
+    ops.clip_gather converts and lays out the frames (HIP kernel on GPU,
+    indexing on CPU), bit-identical to the dataset's. Yields (seq_len, B, 3,
+    S, S) fp32 with the strides of the CUDA branch of `get_generator`: each
+    x[i] is a channels_last frame.
+    """
+    import numpy as np
+
+    from ..ops import clip_gather
+
+    bank = upload_frame_bank(data.load_pack(), device)
+    rng = np.random.RandomState(
+        (torch.initial_seed() + rank * 7919 + (0 if train else 1)) % (2**31))
+    B, T = cfg.batch_size, data.max_seq_len
+
+    def _gen():
+        while True:
+            idx = data.plan_batch(B, rng)
+            seq_len = T
+            if dynamic_length:
+                seq_len = int(rng.randint(T - 2 * data.delta_len, T + 1))
+            yield clip_gather(bank, idx, seq_len)
+
+    return _gen()
+
+
 def get_data_generator(data, train: bool = True, dynamic_length: bool = True, opt=None, rank: int = 0):
     cfg = opt
     device = torch.device(cfg.resolved_device() if hasattr(cfg, "resolved_device") else "cpu")
+    cache = getattr(cfg, "frame_cache", "loader")
+    if cache not in ("loader", "device"):
+        raise ValueError(f"frame_cache must be 'loader' or 'device', got {cache!r}")
+    if cache == "device":
+        if cfg.dataset != "bair":
+            raise ValueError(
+                f"frame_cache='device' needs dataset='bair', got {cfg.dataset!r}")
+        return get_device_bair_generator(data, cfg, device, train, dynamic_length, rank)
     synth = getattr(cfg, "mnist_synth", "loader")
     if synth not in ("loader", "device"):
         raise ValueError(f"mnist_synth must be 'loader' or 'device', got {synth!r}")

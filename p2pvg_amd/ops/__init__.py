@@ -156,10 +156,21 @@ def moving_mnist_render(digits: torch.Tensor, idx: torch.Tensor,
 from .frame_metrics import frame_metrics, frame_metrics_backend  # noqa: E402
 
 
+# ---------------------------------------------------------------------------
+# Batch gather from a device-resident uint8 frame bank
+# ---------------------------------------------------------------------------
+
+# bank (N,T,H,W,C) u8, idx (B,) int32 on the CPU -> (L,B,C,H,W) f32 =
+# bank[idx, :L] / 255 in the generator's layout: HIP kernel on GPU, indexing
+# on CPU. Bound at import for the reason given above.
+from .clip_gather import clip_gather  # noqa: E402
+
+
 __all__ = [
     "lstm_cell",
     "gaussian_kl",
     "moving_mnist_render",
+    "clip_gather",
     "frame_metrics",
     "frame_metrics_backend",
     "backend_mode",

@@ -96,6 +96,7 @@ torch::Tensor moving_mnist_render(torch::Tensor digits, torch::Tensor idx,
                                   torch::Tensor pos, long S);
 std::vector<torch::Tensor> frame_metrics(torch::Tensor a, torch::Tensor b,
                                          torch::Tensor win, double data_range);
+torch::Tensor clip_gather(torch::Tensor bank, torch::Tensor idx, long L);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
@@ -187,4 +188,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "-> (ssim (M) f32, mse (M) f32)",
         pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("win"),
         pybind11::arg("data_range") = 1.0);
+  m.def("clip_gather", &clip_gather,
+        "batch gather from a uint8 frame bank (gfx950); bank (N,T,H,W,C) u8, "
+        "idx (B) i32 host-validated -> (L,B,H,W,C) f32 = bank[idx, :L] / 255, "
+        "correctly rounded",
+        pybind11::arg("bank"), pybind11::arg("idx"), pybind11::arg("L"));
 }
