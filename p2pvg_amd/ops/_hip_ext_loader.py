@@ -1,8 +1,24 @@
 """Loader for the in-tree compiled extension (p2pvg_amd/ops/_C*.so)."""
 from __future__ import annotations
 
+import os
+
+_tail_env_applied = False
+
 
 def load():
+    global _tail_env_applied
     from . import _C  # in-tree .so built by setup_ext.py
 
+    if not _tail_env_applied:
+        # P2PVG_BN_TAIL=fused|split, read once at the first load: the BN
+        # statistics tail as one launch (default) or as the earlier
+        # fold/finalize/combine sequence, for A/B timing. Later loads leave
+        # the mode alone, so _C.set_bn_tail_fused() holds in-process.
+        tail = os.environ.get("P2PVG_BN_TAIL", "fused")
+        if tail not in ("fused", "split"):
+            raise ValueError(
+                f"P2PVG_BN_TAIL must be 'fused' or 'split', got {tail!r}")
+        _C.set_bn_tail_fused(tail == "fused")
+        _tail_env_applied = True
     return _C

@@ -91,6 +91,8 @@ torch::Tensor upsample2x_fwd(torch::Tensor in, long ri, long ro);
 torch::Tensor upsample2x_bwd(torch::Tensor gout, long ri, long ro);
 torch::Tensor channel_sum_nhwc(torch::Tensor x,
                                c10::optional<torch::Tensor> acc);
+void set_bn_tail_fused(bool fused);
+bool bn_tail_fused();
 torch::Tensor sqdiff_sum(torch::Tensor a, torch::Tensor b);
 torch::Tensor moving_mnist_render(torch::Tensor digits, torch::Tensor idx,
                                   torch::Tensor pos, long S);
@@ -150,6 +152,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("channel_sum_nhwc", &channel_sum_nhwc,
         "NHWC per-channel sum, fp32 out (gfx950, deterministic)",
         pybind11::arg("x"), pybind11::arg("acc") = c10::nullopt);
+  m.def("set_bn_tail_fused", &set_bn_tail_fused,
+        "BN statistics tail: true = one fused launch (default), false = the "
+        "split fold/finalize/combine launches (bitwise the same results)",
+        pybind11::arg("fused"));
+  m.def("bn_tail_fused", &bn_tail_fused, "current BN statistics tail mode");
   m.def("conv2d_nhwc_wgrad", &conv2d_nhwc_wgrad,
         "NHWC wgrad, split-K over pixel slabs (gfx950 MFMA, deterministic); "
         "acc: fp32 dense (B,R,S,A)-layout tensor to accumulate into; "

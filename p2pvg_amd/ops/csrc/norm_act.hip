@@ -59,18 +59,69 @@ __device__ __forceinline__ float act_bwd_from_u(float u, int act) {
   }
 }
 
+// Everything bn_act_fwd_train's statistics tail writes per channel.
+struct BnFinalizeArgs {
+  const float* gamma;
+  const float* beta;
+  float* mean_out;
+  float* invstd_out;
+  float* scale_out;
+  float* shift_out;
+  float* running_mean;  // nullptr: no running-stat update
+  float* running_var;
+  float momentum, eps, count;
+};
+
+// channel c's raw sums (s0 = sum x, s1 = sum x^2) -> saved mean/invstd +
+// scale/shift (+ running update). ONE definition for the split and the fused
+// tail: the compiler contracts `s1 / count - m * m` and the running-stat
+// expressions the same way on both paths.
+__device__ __forceinline__ void bn_finalize_channel(const BnFinalizeArgs& a,
+                                                    int c, float s0,
+                                                    float s1) {
+  const float count = a.count;
+  const float m = s0 / count;
+  float var = s1 / count - m * m;
+  var = var > 0.f ? var : 0.f;
+  const float inv = rsqrtf(var + a.eps);
+  a.mean_out[c] = m;
+  a.invstd_out[c] = inv;
+  const float g = a.gamma[c], b = a.beta[c];
+  a.scale_out[c] = g * inv;
+  a.shift_out[c] = b - m * g * inv;
+  if (a.running_mean != nullptr) {
+    const float momentum = a.momentum;
+    a.running_mean[c] = (1.f - momentum) * a.running_mean[c] + momentum * m;
+    const float ub = var * (count / fmaxf(count - 1.f, 1.f));
+    a.running_var[c] = (1.f - momentum) * a.running_var[c] + momentum * ub;
+  }
+}
+
+// column i of the (2, C) backward sums: red_final, and dbeta (= s1, i < C) /
+// dgamma (= s2, i >= C) stored or accumulated.
+__device__ __forceinline__ void bn_red_store(int i, float t,
+                                             float* __restrict__ red_final,
+                                             float* __restrict__ dgamma,
+                                             float* __restrict__ dbeta, int C,
+                                             int accumulate) {
+  red_final[i] = t;
+  if (i < C) {
+    if (dbeta != nullptr) dbeta[i] = accumulate ? dbeta[i] + t : t;
+  } else {
+    if (dgamma != nullptr)
+      dgamma[i - C] = accumulate ? dgamma[i - C] + t : t;
+  }
+}
+
+__device__ __forceinline__ void channel_sum_store(long c, float t,
+                                                  float* __restrict__ out,
+                                                  int accumulate) {
+  out[c] = accumulate ? out[c] + t : t;
+}
+
 // stats (2,K) raw sums -> saved mean/invstd + scale/shift (+ running update)
 __global__ void bn_finalize_kernel(const float* __restrict__ stats,
-                                   const float* __restrict__ gamma,
-                                   const float* __restrict__ beta,
-                                   float* __restrict__ mean_out,
-                                   float* __restrict__ invstd_out,
-                                   float* __restrict__ scale_out,
-                                   float* __restrict__ shift_out,
-                                   float* __restrict__ running_mean,
-                                   float* __restrict__ running_var,
-                                   float momentum, float eps, float count,
-                                   int K, int nbuckets) {
+                                   BnFinalizeArgs a, int K, int nbuckets) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= K) return;
   float s0 = 0.f, s1 = 0.f;
@@ -78,20 +129,7 @@ __global__ void bn_finalize_kernel(const float* __restrict__ stats,
     s0 += stats[(long)b * 2 * K + c];
     s1 += stats[(long)b * 2 * K + K + c];
   }
-  const float m = s0 / count;
-  float var = s1 / count - m * m;
-  var = var > 0.f ? var : 0.f;
-  const float inv = rsqrtf(var + eps);
-  mean_out[c] = m;
-  invstd_out[c] = inv;
-  const float g = gamma[c], b = beta[c];
-  scale_out[c] = g * inv;
-  shift_out[c] = b - m * g * inv;
-  if (running_mean != nullptr) {
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-    const float ub = var * (count / fmaxf(count - 1.f, 1.f));
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * ub;
-  }
+  bn_finalize_channel(a, c, s0, s1);
 }
 
 // eval mode: scale/shift straight from running stats
@@ -397,13 +435,7 @@ __global__ void bn_red_combine_kernel(const float* __restrict__ rows,
        i += gridDim.x * blockDim.x) {
     float t = 0.f;
     for (int r = 0; r < nrows; ++r) t += rows[(long)r * 2 * C + i];
-    red_final[i] = t;
-    if (i < C) {
-      if (dbeta != nullptr) dbeta[i] = accumulate ? dbeta[i] + t : t;
-    } else {
-      if (dgamma != nullptr)
-        dgamma[i - C] = accumulate ? dgamma[i - C] + t : t;
-    }
+    bn_red_store(i, t, red_final, dgamma, dbeta, C, accumulate);
   }
 }
 
@@ -456,7 +488,7 @@ __global__ void rows_combine_kernel(const float* __restrict__ rows, int nrows,
        c += (long)gridDim.x * blockDim.x) {
     float t = 0.f;
     for (int r = 0; r < nrows; ++r) t += rows[(long)r * C + c];
-    out[c] = accumulate ? out[c] + t : t;
+    channel_sum_store(c, t, out, accumulate);
   }
 }
 
@@ -572,7 +604,273 @@ torch::Tensor reduce_rows_det(torch::Tensor rows, long C) {
   return rows;
 }
 
+// ---------------------------------------------------------------------------
+// Fused statistics tail: ONE launch per BN pass finishes the per-column sums
+// of a (R, ld) fp32 partial-row matrix and does the finalize / combine
+// arithmetic. The association is the split path's (reduce_rows_det + serial
+// walk), so results are bit-identical: 64-row chunks summed serially from
+// 0.f in row order, again while more than 64 rows remain, then one serial
+// walk. Only the LOADS of a chunk overlap; the adds stay in order.
+//   level 1: block (column block, chunk p) sums rows [64p, 64p+64) and stores
+//            partial row p with plain stores;
+//   hand-off: one ticket counter per column block (zeroed by a memset node
+//            ahead of the launch). Nobody waits: the block that draws the
+//            last ticket acquires and does every remaining level for its own
+//            columns, then the arithmetic. See docs/KERNELS.md for why each
+//            step of the hand-off is there.
+// R <= 64 needs neither level 1 nor the ticket: one block row walks the input.
+// ---------------------------------------------------------------------------
+constexpr int TAIL_CHUNK = 64;
+constexpr int TAIL_MAX_BLOCK = 256;
+
+bool g_bn_tail_fused = true;
+
+// serial sum from 0.f, in row order, of rows [b0, b1) of the column p points
+// into; loads issued 16 rows at a time ahead of the dependent adds.
+__device__ __forceinline__ float tail_walk(const float* p, long ld, int b0,
+                                           int b1) {
+  float t = 0.f;
+  for (int b = b0; b < b1; b += 16) {
+    float v[16];
+    if (b + 16 <= b1) {  // whole batch: no per-row tests
+#pragma unroll
+      for (int j = 0; j < 16; ++j) v[j] = p[(long)(b + j) * ld];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) t += v[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        v[j] = b + j < b1 ? p[(long)(b + j) * ld] : 0.f;
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        if (b + j < b1) t += v[j];
+    }
+  }
+  return t;
+}
+
+// one fold level inside the last block: n rows of one column -> ceil(n/64)
+// rows, eight chunks' chains side by side (64 loads in flight per thread),
+// each chain serial and in row order.
+__device__ __forceinline__ void tail_fold(const float* src, float* dst,
+                                          long ld, int n) {
+  const int n2 = (n + TAIL_CHUNK - 1) / TAIL_CHUNK;
+  for (int q0 = 0; q0 < n2; q0 += 8) {
+    float t[8];
+#pragma unroll
+    for (int g = 0; g < 8; ++g) t[g] = 0.f;
+    const bool whole = (q0 + 8) * TAIL_CHUNK <= n;  // no per-row tests
+    for (int r = 0; r < TAIL_CHUNK; r += 8) {
+      float v[8][8];
+      if (whole) {
+#pragma unroll
+        for (int g = 0; g < 8; ++g) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            v[g][j] = src[(long)((q0 + g) * TAIL_CHUNK + r + j) * ld];
+        }
+#pragma unroll
+        for (int g = 0; g < 8; ++g) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) t[g] += v[g][j];
+        }
+        continue;
+      }
+#pragma unroll
+      for (int g = 0; g < 8; ++g) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int row = (q0 + g) * TAIL_CHUNK + r + j;
+          v[g][j] = row < n ? src[(long)row * ld] : 0.f;
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < 8; ++g) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int row = (q0 + g) * TAIL_CHUNK + r + j;
+          if (row < n) t[g] += v[g][j];
+        }
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < 8; ++g)
+      if (q0 + g < n2) dst[(long)(q0 + g) * ld] = t[g];
+  }
+}
+
+// Column `col` of rows (R, ld) summed in the fixed association. Grid is
+// (column blocks, R > 64 ? ceil(R/64) : 1). Returns false in every block
+// that is done after level 1; true, with the column's total, in the block
+// that finishes the column block. Threads with !valid carry a clamped col:
+// they load, never store, and take part in every barrier.
+// ws: (gridDim.y + ceil(gridDim.y/64), ld) floats, not initialised;
+// cnt: one zeroed word per column block; sm: TAIL_MAX_BLOCK + 1 words.
+__device__ __forceinline__ bool tail_reduce(const float* __restrict__ rows,
+                                            float* ws, unsigned* cnt, int R,
+                                            long ld, long col, bool valid,
+                                            unsigned* sm, float& total) {
+  const float* src = rows + col;
+  int n = R;
+  if (R > TAIL_CHUNK) {
+    const int p = blockIdx.y;
+    const int R1 = gridDim.y;
+    const float t = tail_walk(rows + col, ld, p * TAIL_CHUNK,
+                              min(p * TAIL_CHUNK + TAIL_CHUNK, R));
+    if (valid) ws[(long)p * ld + col] = t;
+    // publish: every wave drains its stores, then ONE agent-scope release,
+    // a second drain (the fence's own wait can be dropped), then the ticket.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const unsigned ticket = __hip_atomic_fetch_add(
+          cnt + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned last = ticket == (unsigned)R1 - 1u ? 1u : 0u;
+      if (last) {
+        // consume: one agent-scope acquire, its wait, then the barrier below
+        // holds the other waves' loads behind the invalidate.
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      sm[TAIL_MAX_BLOCK] = last;
+    }
+    __syncthreads();
+    if (!sm[TAIL_MAX_BLOCK]) return false;
+    // remaining levels: each thread touches only its own column, ping-pong
+    // between the level-1 rows and the spare rows behind them.
+    float* a = ws;
+    float* b = ws + (long)R1 * ld;
+    n = R1;
+    while (n > TAIL_CHUNK) {
+      if (valid) tail_fold(a + col, b + col, ld, n);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      n = (n + TAIL_CHUNK - 1) / TAIL_CHUNK;
+      float* s = a;
+      a = b;
+      b = s;
+    }
+    src = a + col;
+  }
+  total = tail_walk(src, ld, 0, n);
+  return true;
+}
+
+// forward: thread t < half owns channel ch's sum column, thread t + half its
+// sum-of-squares column (K + ch); the pair meets through LDS for finalize.
+__global__ __launch_bounds__(TAIL_MAX_BLOCK) void bn_tail_fwd_kernel(
+    const float* __restrict__ stats, float* ws, unsigned* cnt,
+    BnFinalizeArgs a, int K, int R, int half) {
+  __shared__ unsigned sm[TAIL_MAX_BLOCK + 1];
+  const int which = (int)threadIdx.x >= half ? 1 : 0;
+  const int ch = blockIdx.x * half + (int)threadIdx.x - which * half;
+  const bool valid = ch < K;
+  const long col = valid ? (long)which * K + ch : 0;
+  float t;
+  if (!tail_reduce(stats, ws, cnt, R, 2L * K, col, valid, sm, t)) return;
+  if (which) sm[threadIdx.x - half] = __float_as_uint(t);
+  __syncthreads();
+  if (!which && valid)
+    bn_finalize_channel(a, ch, t, __uint_as_float(sm[threadIdx.x]));
+}
+
+__global__ __launch_bounds__(TAIL_MAX_BLOCK) void bn_tail_bwd_kernel(
+    const float* __restrict__ rows, float* ws, unsigned* cnt,
+    float* __restrict__ red_final, float* __restrict__ dgamma,
+    float* __restrict__ dbeta, int C, int R, int accumulate) {
+  __shared__ unsigned sm[TAIL_MAX_BLOCK + 1];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = i < 2 * C;
+  float t;
+  if (!tail_reduce(rows, ws, cnt, R, 2L * C, valid ? i : 0, valid, sm, t))
+    return;
+  if (valid) bn_red_store(i, t, red_final, dgamma, dbeta, C, accumulate);
+}
+
+__global__ __launch_bounds__(TAIL_MAX_BLOCK) void bn_tail_csum_kernel(
+    const float* __restrict__ rows, float* ws, unsigned* cnt,
+    float* __restrict__ out, int C, int R, int accumulate) {
+  __shared__ unsigned sm[TAIL_MAX_BLOCK + 1];
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = c < C;
+  float t;
+  if (!tail_reduce(rows, ws, cnt, R, (long)C, valid ? c : 0, valid, sm, t))
+    return;
+  if (valid) channel_sum_store(c, t, out, accumulate);
+}
+
+// Workspace and ticket counters of one tail launch over R rows of ld floats.
+// The counters are an allocation of their own, a multiple of 16 bytes, zeroed
+// on the stream by a memset (a memset node under graph capture, no fill
+// kernel); the workspace is never initialised.
+struct TailPlan {
+  int R1 = 1;  // grid y
+  torch::Tensor ws, cnt;
+  float* wsp = nullptr;
+  unsigned* cntp = nullptr;
+};
+
+TailPlan tail_plan(const torch::Tensor& like, int R, long ld, int colblocks,
+                   hipStream_t stream) {
+  TailPlan p;
+  if (R <= TAIL_CHUNK) return p;
+  p.R1 = ceil_div(R, TAIL_CHUNK);
+  const int spare = ceil_div(p.R1, TAIL_CHUNK);
+  p.ws = torch::empty({(long)p.R1 + spare, ld},
+                      like.options().dtype(torch::kFloat32));
+  const long nwords = (long)ceil_div(colblocks, 4) * 4;
+  p.cnt = torch::empty({nwords}, like.options().dtype(torch::kInt32));
+  p.wsp = p.ws.data_ptr<float>();
+  p.cntp = reinterpret_cast<unsigned*>(p.cnt.data_ptr<int>());
+  TORCH_CHECK(hipMemsetAsync(p.cntp, 0, nwords * sizeof(unsigned), stream) ==
+                  hipSuccess,
+              "bn tail: counter memset failed");
+  return p;
+}
+
+// threads per block for `ncols` single-column threads: whole waves, no more
+// than the columns need.
+int tail_block(long ncols) {
+  return (int)std::min<long>(TAIL_MAX_BLOCK, (ncols + 63) / 64 * 64);
+}
+
+void bn_tail_fwd(const torch::Tensor& stats, const BnFinalizeArgs& fa, int C,
+                 int R, hipStream_t stream) {
+  const int half = std::min(TAIL_MAX_BLOCK / 2, (C + 31) / 32 * 32);
+  const int colblocks = ceil_div(C, half);
+  TailPlan p = tail_plan(stats, R, 2L * C, colblocks, stream);
+  hipLaunchKernelGGL(bn_tail_fwd_kernel, dim3(colblocks, p.R1),
+                     dim3(2 * half), 0, stream, stats.data_ptr<float>(), p.wsp,
+                     p.cntp, fa, C, R, half);
+}
+
+void bn_tail_bwd(const torch::Tensor& rows, int R, float* red, float* dgamma,
+                 float* dbeta, int C, int accumulate, hipStream_t stream) {
+  const int bt = tail_block(2L * C);
+  const int colblocks = ceil_div(2 * C, bt);
+  TailPlan p = tail_plan(rows, R, 2L * C, colblocks, stream);
+  hipLaunchKernelGGL(bn_tail_bwd_kernel, dim3(colblocks, p.R1), dim3(bt), 0,
+                     stream, rows.data_ptr<float>(), p.wsp, p.cntp, red,
+                     dgamma, dbeta, C, R, accumulate);
+}
+
+void bn_tail_csum(const torch::Tensor& rows, int R, float* out, int C,
+                  int accumulate, hipStream_t stream) {
+  const int bt = tail_block(C);
+  const int colblocks = ceil_div(C, bt);
+  TailPlan p = tail_plan(rows, R, (long)C, colblocks, stream);
+  hipLaunchKernelGGL(bn_tail_csum_kernel, dim3(colblocks, p.R1), dim3(bt), 0,
+                     stream, rows.data_ptr<float>(), p.wsp, p.cntp, out, C, R,
+                     accumulate);
+}
+
 }  // namespace
+
+// fused (default) or split statistics tail; the split sequence stays for
+// in-process bitwise tests and A/B timing.
+void set_bn_tail_fused(bool fused) { g_bn_tail_fused = fused; }
+bool bn_tail_fused() { return g_bn_tail_fused; }
 
 // Training fwd: x conv output (already stats-accumulated if stats given,
 // else stats computed here via torch ops on the wrapper side).
@@ -598,18 +896,23 @@ std::vector<torch::Tensor> bn_act_fwd_train(
   auto stream = at::cuda::getCurrentCUDAStream();
 
   int nbuckets = stats.dim() == 3 ? (int)stats.size(0) : 1;
-  if (nbuckets > 64) {
-    stats = reduce_rows_det(stats, 2L * C);
-    nbuckets = (int)stats.size(0);
+  const BnFinalizeArgs fa{
+      gamma.data_ptr<float>(), beta.data_ptr<float>(),
+      mean.data_ptr<float>(), invstd.data_ptr<float>(),
+      scale.data_ptr<float>(), shift.data_ptr<float>(),
+      running_mean.has_value() ? running_mean->data_ptr<float>() : nullptr,
+      running_var.has_value() ? running_var->data_ptr<float>() : nullptr,
+      (float)momentum, (float)eps, (float)count};
+  if (g_bn_tail_fused) {
+    bn_tail_fwd(stats, fa, C, nbuckets, stream);
+  } else {
+    if (nbuckets > 64) {
+      stats = reduce_rows_det(stats, 2L * C);
+      nbuckets = (int)stats.size(0);
+    }
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(ceil_div(C, 256)), dim3(256),
+                       0, stream, stats.data_ptr<float>(), fa, C, nbuckets);
   }
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(ceil_div(C, 256)), dim3(256), 0,
-                     stream, stats.data_ptr<float>(), gamma.data_ptr<float>(),
-                     beta.data_ptr<float>(), mean.data_ptr<float>(),
-                     invstd.data_ptr<float>(), scale.data_ptr<float>(),
-                     shift.data_ptr<float>(),
-                     running_mean.has_value() ? running_mean->data_ptr<float>() : nullptr,
-                     running_var.has_value() ? running_var->data_ptr<float>() : nullptr,
-                     (float)momentum, (float)eps, (float)count, C, nbuckets);
 
   const long nvec = x.numel() / 8;
   if (ring > 0) {
@@ -720,16 +1023,21 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor x, torch::Tensor dy,
   torch::Tensor dgamma =
       accumulate ? dgamma_acc.value() : torch::empty({C}, f32);
   torch::Tensor dbeta = accumulate ? dbeta_acc.value() : torch::empty({C}, f32);
-  torch::Tensor folded = rows;
-  int nrows = rgrid;
-  if (nrows > 64) {
-    folded = reduce_rows_det(rows, 2L * C);
-    nrows = (int)folded.size(0);
+  if (g_bn_tail_fused) {
+    bn_tail_bwd(rows, rgrid, red.data_ptr<float>(), dgamma.data_ptr<float>(),
+                dbeta.data_ptr<float>(), C, accumulate, stream);
+  } else {
+    torch::Tensor folded = rows;
+    int nrows = rgrid;
+    if (nrows > 64) {
+      folded = reduce_rows_det(rows, 2L * C);
+      nrows = (int)folded.size(0);
+    }
+    hipLaunchKernelGGL(bn_red_combine_kernel, dim3(ceil_div(2 * C, 256)),
+                       dim3(256), 0, stream, folded.data_ptr<float>(), nrows,
+                       red.data_ptr<float>(), dgamma.data_ptr<float>(),
+                       dbeta.data_ptr<float>(), C, accumulate);
   }
-  hipLaunchKernelGGL(bn_red_combine_kernel, dim3(ceil_div(2 * C, 256)),
-                     dim3(256), 0, stream, folded.data_ptr<float>(), nrows,
-                     red.data_ptr<float>(), dgamma.data_ptr<float>(),
-                     dbeta.data_ptr<float>(), C, accumulate);
   if (ring > 0) {
     hipLaunchKernelGGL(bn_act_bwd_apply_ring_kernel,
                        dim3(std::min(2048, NROWS)), dim3(BLOCK), 0, stream,
@@ -797,6 +1105,10 @@ torch::Tensor channel_sum_nhwc(torch::Tensor x,
                        (BLOCK / 64) * C * sizeof(float), stream,
                        reinterpret_cast<const __bf16*>(x.data_ptr()),
                        rows.data_ptr<float>(), nvec, C);
+  }
+  if (g_bn_tail_fused) {
+    bn_tail_csum(rows, grid, out.data_ptr<float>(), C, accumulate, stream);
+    return out;
   }
   if (grid > 64) {
     rows = reduce_rows_det(rows, (long)C);
