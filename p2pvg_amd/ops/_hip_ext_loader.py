@@ -19,6 +19,15 @@ def load():
         if tail not in ("fused", "split"):
             raise ValueError(
                 f"P2PVG_BN_TAIL must be 'fused' or 'split', got {tail!r}")
+        # P2PVG_WGRAD_ROWS=rows|pertap, likewise: whether the automatic
+        # choice may send the 64-wide 3x3 weight-gradient classes to the
+        # row-order all-taps kernel (default) or keeps them on the per-tap
+        # kernel, for A/B timing. The results are bitwise the same.
+        rows = os.environ.get("P2PVG_WGRAD_ROWS", "rows")
+        if rows not in ("rows", "pertap"):
+            raise ValueError(
+                f"P2PVG_WGRAD_ROWS must be 'rows' or 'pertap', got {rows!r}")
         _C.set_bn_tail_fused(tail == "fused")
+        _C.set_wgrad_rows(rows == "rows")
         _tail_env_applied = True
     return _C

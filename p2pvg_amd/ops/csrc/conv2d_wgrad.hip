@@ -1018,6 +1018,286 @@ __global__ __launch_bounds__(THREADS) void conv2d_wgrad_taps_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------
+// Row-order all-taps 3x3 wgrad for 64-wide maps: the single-pass kernel above
+// with one-row chunks, so that every weight-gradient element is summed in
+// exactly the per-tap kernel's order. (stride 1, PAD == 0 over a zero-ringed
+// X, WO == 64, B, A1 and A multiples of 64, any yring.)
+//
+// What fixes the bits. A chunk is 64 consecutive output pixels, which on a
+// 64-wide map is one output row; its two MFMA K-steps are columns 0-31 and
+// 32-63, lane group lane>>4 holding pixels g*8..g*8+7 of the step; the slabs
+// are the per-tap path's (whole rows, because p_per_slab is 64-aligned) and
+// each element has one accumulator chain per slab. The tile shape, the wave
+// layout and the LDS layout do not enter the sums.
+//
+// X side: each input row is staged ONCE as three column-shifted
+// [64 pix][64 ch] subtiled images (24 KB); tap (r,s) of output row ho is the
+// aligned tr16 read of image s of input row ho + r. A chunk needs input rows
+// ho..ho+2, two of which the chunks before it staged: in steady state a
+// chunk stages one row plus one Y image, 24 KB + 8 KB against 9 x 16 KB.
+//
+// Segments. The chunks of a slab fall into segments of consecutive rows of
+// one image; a segment begins at the slab start and at every image boundary
+// and needs three fresh rows there. Each segment runs as a pipeline of its
+// own: its first chunk's three rows and Y are staged into ring slots 0..2 /
+// Y buffer 0 after a barrier that retires the segment before it, so nothing
+// from two segments is ever in flight together. That stall is paid once per
+// 64 chunks at most and keeps the ring at RW_NR = 5 slots: at the top of
+// iteration t chunk t reads rows t..t+2, chunk t+1's row t+3 is in flight and
+// chunk t+2's row t+4 goes to slot (t+4) % 5, which held row t-1, last read
+// by chunk t-1 before the barrier. Y rotates through 3 buffers the same way.
+//
+// vmcnt. Within a segment a wave issues, in this order,
+//   S(0) = 3 * RW_XC + YC calls, S(1) = G, [wait_0] S(2) = G, [wait_1] ...
+// with G = RW_XC + YC for every chunk but the first. At wait_t the calls
+// issued after S(t) are exactly S(t+1) when chunk t+1 exists (S(t+2) follows
+// the wait), so vmcnt(G) retires S(t), whatever S(t) itself counted; on the
+// segment's last chunk nothing follows and the wait is vmcnt(0). A segment
+// therefore ends with no loads outstanding and the next starts from zero:
+// there is no steady-after-restart or restart-after-steady mix to count.
+//
+// Tiles: BTB = 64 is the 64(b) x 64(a) tile of the strip kernel (waves 2 x 2,
+// 36 fragments each); BTB = 32 halves the tile in b (waves 1 x 4, each
+// 32(b) x 16(a) x 9 taps = 18 fragments) and doubles the blocks for layers
+// whose slabs alone do not fill the CUs.
+
+constexpr int RW = 64;                 // map width = pixels per row image
+constexpr int RW_IMG = RW * 64 * 2;    // one shifted row image, 8 KB
+constexpr int RW_ROW = 3 * RW_IMG;     // the three shifts of one row, 24 KB
+constexpr int RW_NR = 5;               // row ring slots
+constexpr int RW_XC = RW_ROW / 4096;   // glds calls per wave per row
+
+template <int BTB>
+struct RowsCfg {
+  static constexpr int YIMG = PCH * BTB * 2;  // Y image of one chunk
+  static constexpr int YC = YIMG / 4096;      // glds calls per wave (Y)
+  static constexpr int G = RW_XC + YC;        // calls per wave, steady chunk
+  static constexpr int LDS = RW_NR * RW_ROW + 3 * YIMG;  // 144 / 132 KB
+  static constexpr int XF = BTB / 32;         // X fragments per wave and tap
+  static constexpr int YHALF = (BTB / 16) * 128;  // next pixel-group row of Y
+};
+
+// tr16 pair at an immediate offset; HALF is the byte distance to the next
+// pixel-group row of the image (second half of the 8-pixel run)
+template <int OFF, int HALF>
+__device__ __forceinline__ void tr16_issue_off(unsigned addr, u16x4& lo,
+                                               u16x4& hi) {
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
+               : "=v"(lo)
+               : "v"(addr), "n"(OFF));
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
+               : "=v"(hi)
+               : "v"(addr), "n"(OFF + HALF));
+}
+
+template <int N>
+__device__ __forceinline__ void rows_wait(u16x4 (&lo)[2], u16x4 (&hi)[2]) {
+  taps_wait<N>(lo[0], hi[0], lo[1], hi[1]);
+}
+template <int N>
+__device__ __forceinline__ void rows_wait(u16x4 (&lo)[1], u16x4 (&hi)[1]) {
+  asm volatile("s_waitcnt lgkmcnt(%2)"
+               : "+v"(lo[0]), "+v"(hi[0])
+               : "n"(N)
+               : "memory");
+}
+
+// the X fragments of tap TP (image TP % 3 of the row at `ra`), K-step KK
+template <int XF, int TP, int KK>
+__device__ __forceinline__ void rows_issue_x(unsigned ra, u16x4 (&lo)[XF],
+                                             u16x4 (&hi)[XF]) {
+  constexpr int off = (TP % 3) * RW_IMG + KK * 8 * 512;
+  tr16_issue_off<off, 512>(ra, lo[0], hi[0]);
+  if constexpr (XF == 2) tr16_issue_off<off + 128, 512>(ra, lo[1], hi[1]);
+}
+
+template <int XF>
+__device__ __forceinline__ void rows_mma(f32x4 (&acc)[2][XF],
+                                         const u16x4 (&ylo)[2],
+                                         const u16x4 (&yhi)[2],
+                                         const u16x4 (&xlo)[XF],
+                                         const u16x4 (&xhi)[XF]) {
+  bf16x8 yf[2], xf[XF];
+#pragma unroll
+  for (int f = 0; f < 2; ++f) yf[f] = tr16_combine(ylo[f], yhi[f]);
+#pragma unroll
+  for (int f = 0; f < XF; ++f) xf[f] = tr16_combine(xlo[f], xhi[f]);
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < XF; ++j)
+      acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(yf[i], xf[j],
+                                                          acc[i][j], 0, 0, 0);
+}
+
+// one 32-pixel K-step of a chunk for all nine taps: the reads of tap tp+1
+// are in flight while tap tp multiplies. Each tap issues 2*XF reads and LDS
+// reads return in order, so lgkmcnt(2*XF) after issuing tap tp+1 retires tap
+// tp (and, at tp == 0, the Y reads issued before it).
+template <int BTB, int KK>
+__device__ __forceinline__ void rows_kstep(
+    unsigned ya, const unsigned (&rowa)[3],
+    f32x4 (&acc)[9][2][RowsCfg<BTB>::XF]) {
+  using C = RowsCfg<BTB>;
+  constexpr int XF = C::XF;
+  constexpr int yk = KK * 8 * C::YHALF;  // pixels KK*32.. of the Y image
+  u16x4 ylo[2], yhi[2], xlo[2][XF], xhi[2][XF];
+  tr16_issue_off<yk, C::YHALF>(ya, ylo[0], yhi[0]);
+  tr16_issue_off<yk + 128, C::YHALF>(ya, ylo[1], yhi[1]);
+  rows_issue_x<XF, 0, KK>(rowa[0], xlo[0], xhi[0]);
+#define RW_TAP(TP)                                                     \
+  rows_issue_x<XF, (TP) + 1, KK>(rowa[((TP) + 1) / 3], xlo[((TP) + 1) & 1], \
+                                 xhi[((TP) + 1) & 1]);                 \
+  if ((TP) == 0) rows_wait<2 * XF>(ylo, yhi);                          \
+  rows_wait<2 * XF>(xlo[(TP) & 1], xhi[(TP) & 1]);                     \
+  rows_mma<XF>(acc[TP], ylo, yhi, xlo[(TP) & 1], xhi[(TP) & 1]);
+  RW_TAP(0) RW_TAP(1) RW_TAP(2) RW_TAP(3) RW_TAP(4) RW_TAP(5) RW_TAP(6)
+  RW_TAP(7)
+#undef RW_TAP
+  rows_wait<0>(xlo[0], xhi[0]);
+  rows_mma<XF>(acc[8], ylo, yhi, xlo[0], xhi[0]);
+}
+
+template <int BTB>
+__global__ __launch_bounds__(THREADS) void conv2d_wgrad_rows_kernel(
+    const __bf16* __restrict__ Y, const __bf16* __restrict__ X,
+    const __bf16* __restrict__ X2, float* __restrict__ ws, int HO, int B,
+    int H, int W, int A, int A1, int yring, int nchunks, int cps, int ho_sh) {
+  using C = RowsCfg<BTB>;
+  constexpr int XF = C::XF;
+  extern __shared__ __align__(16) char rlds[];
+  char* const ybufs = rlds + RW_NR * RW_ROW;
+
+  const int at_blocks = A >> 6;
+  const int b0 = (blockIdx.x / at_blocks) * BTB;
+  const int a0 = (blockIdx.x % at_blocks) * 64;
+  const int c_begin = blockIdx.z * cps;
+  const int c_end = min(c_begin + cps, nchunks);
+
+  const int tid = threadIdx.x;
+  const int wid = tid >> 6;
+  const int lane = tid & 63;
+  const int wm = BTB == 64 ? (wid >> 1) * 32 : 0;
+  const int wn = BTB == 64 ? (wid & 1) * 32 : wid * 16;
+  const int HOp = HO + 2 * yring;
+  const int WOp = RW + 2 * yring;
+
+  // dual-X: the 64-wide a-tile lies wholly in one source (A1 % 64 == 0)
+  const bool second = X2 != nullptr && a0 >= A1;
+  const __bf16* xsrc = second ? X2 + (a0 - A1) : X + a0;
+  const int as = X2 == nullptr ? A : (second ? A - A1 : A1);
+  const __bf16* ysrc = Y + b0;
+
+  // per-lane staging offsets (elements), fixed for the whole kernel
+  int xl_off[RW_XC], yl_off[C::YC];
+#pragma unroll
+  for (int i = 0; i < RW_XC; ++i) {
+    const int q = wid * RW_XC + i;  // 1 KB unit of the 24 KB row: image q/8
+    int pixl, ch0;
+    glds_decode((q & 7) * 64 + lane, 2, pixl, ch0);
+    xl_off[i] = (pixl + (q >> 3)) * as + ch0;   // column pixl + s <= 65
+  }
+#pragma unroll
+  for (int i = 0; i < C::YC; ++i) {
+    int pixl, ch0;
+    glds_decode((wid * C::YC + i) * 64 + lane, BTB == 64 ? 2 : 1, pixl, ch0);
+    yl_off[i] = pixl * B + ch0;
+  }
+
+  auto stage_row = [&](int n, int hi, int slot) {
+    const __bf16* rb = xsrc + (long)(n * H + hi) * W * as;
+    char* l = rlds + slot * RW_ROW + wid * RW_XC * 1024;
+#pragma unroll
+    for (int i = 0; i < RW_XC; ++i) wglds16(rb + xl_off[i], l + i * 1024);
+  };
+  auto stage_y = [&](int n, int ho, int ybuf) {
+    const __bf16* yb =
+        ysrc + (((long)n * HOp + ho + yring) * WOp + yring) * B;
+    char* l = ybufs + ybuf * C::YIMG + wid * C::YC * 1024;
+#pragma unroll
+    for (int i = 0; i < C::YC; ++i) wglds16(yb + yl_off[i], l + i * 1024);
+  };
+
+  f32x4 acc[9][2][XF];
+#pragma unroll
+  for (int tp = 0; tp < 9; ++tp)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < XF; ++j) acc[tp][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // per-lane tr16 bases: pixel run (lane>>4)*8 = two pixel-group rows, column
+  // lane&15 of the wave's first channel subtile
+  const unsigned yrd = (unsigned)(unsigned long long)ybufs +
+                       (unsigned)((lane >> 4) * 2 * C::YHALF +
+                                  (lane & 15) * 8 + (wm >> 4) * 128);
+  const unsigned xrd = (unsigned)(unsigned long long)rlds +
+                       (unsigned)((lane >> 4) * 2 * 512 + (lane & 15) * 8 +
+                                  (wn >> 4) * 128);
+
+  const int ho_mask = (1 << ho_sh) - 1;
+  int c = c_begin;
+  while (c < c_end) {
+    const int n = c >> ho_sh;
+    const int ho0 = c & ho_mask;
+    const int len = min(HO - ho0, c_end - c);
+    // the segment before this one ended on vmcnt(0); once every wave has
+    // left its last chunk the whole ring is free
+    if (c != c_begin) wbarrier_mem();
+    stage_row(n, ho0, 0);
+    stage_row(n, ho0 + 1, 1);
+    stage_row(n, ho0 + 2, 2);
+    stage_y(n, ho0, 0);
+    if (len > 1) {
+      stage_row(n, ho0 + 3, 3);
+      stage_y(n, ho0 + 1, 1);
+    }
+    int s0 = 0;    // ring slot of chunk t's first row
+    int snew = 4;  // ring slot chunk t+2's new row goes to
+    int ybuf = 0;
+    for (int t = 0; t < len; ++t) {
+      if (t + 1 < len) wwaitcnt_vm<C::G>();
+      else wwaitcnt_vm<0>();
+      wbarrier_mem();
+      // slot snew and Y buffer (t+2)%3 were last read by chunk t-1
+      if (t + 2 < len) {
+        stage_row(n, ho0 + t + 4, snew);
+        stage_y(n, ho0 + t + 2, ybuf >= 1 ? ybuf - 1 : 2);
+      }
+      unsigned rowa[3];
+      int slot = s0;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        rowa[j] = xrd + (unsigned)(slot * RW_ROW);
+        slot = slot + 1 == RW_NR ? 0 : slot + 1;
+      }
+      const unsigned ya = yrd + (unsigned)(ybuf * C::YIMG);
+      rows_kstep<BTB, 0>(ya, rowa, acc);
+      rows_kstep<BTB, 1>(ya, rowa, acc);
+      s0 = s0 + 1 == RW_NR ? 0 : s0 + 1;
+      snew = snew + 1 == RW_NR ? 0 : snew + 1;
+      ybuf = ybuf == 2 ? 0 : ybuf + 1;
+    }
+    c += len;
+  }
+
+  float* slab = ws + (long)blockIdx.z * B * 9 * A;
+#pragma unroll
+  for (int tp = 0; tp < 9; ++tp)
+#pragma unroll
+    for (int j = 0; j < XF; ++j) {
+      const int a = a0 + wn + j * 16 + (lane & 15);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int b = b0 + wm + i * 16 + (lane >> 4) * 4 + v;
+          slab[((long)b * 9 + tp) * A + a] = acc[tp][i][j][v];
+        }
+    }
+}
+
 // out[e] (+)= sum over slabs ws[z][e] — serial over z (deterministic).
 __global__ __launch_bounds__(256) void wgrad_combine_kernel(
     const float* __restrict__ ws, float* __restrict__ out, int sp, long E,
@@ -1062,14 +1342,60 @@ __global__ __launch_bounds__(CGR * CEL) void wgrad_combine2_kernel(
   }
 }
 
-// (B, A, width) classes auto sends to the all-taps kernel: the 32-wide ones
-// measured in profiles/prof_wgrad_b512.txt (B 64..128, A 64..256). There the
-// result is bitwise the per-tap path's, so training results do not move.
-// Wider maps are faster still but sum in strip order: a different fp32
-// rounding of ~1e-6, which a training step amplifies (see ROADMAP); they
-// stay on the per-tap path.
+// (B, A, width) classes auto sends to the strip all-taps kernel: the 32-wide
+// ones measured in profiles/prof_wgrad_b512.txt (B 64..128, A 64..256). There
+// the result is bitwise the per-tap path's, so training results do not move.
+// On wider maps the strip kernel sums in strip order: a different fp32
+// rounding of ~1e-6, which a training step amplifies (see ROADMAP), so auto
+// never sends them there. 64-wide maps have the row-order kernel instead
+// (rows_auto below), whose sums are the per-tap path's bit for bit; 128-wide
+// maps stay on the per-tap path.
 bool taps_auto(int B, int A, int WO) {
   return B <= 128 && A <= 256 && WO == 32;
+}
+
+// (B, A) classes of 64-wide maps auto sends to the row-order all-taps kernel:
+// those whose per-call time (kernel plus combine, per-tap slabs, batch 512)
+// beat the per-tap path by more than the run-to-run spread in
+// profiles/prof_wgrad_rows_b512.txt: the two of the 64-pixel model (c1.1
+// 64x64 2.85x, upc5.0 64x(64+64) 2.94x) and the four the 128-pixel model
+// reaches (B or A of 128, A up to 128+128: 1.95x-2.97x). Wider channel
+// counts on a 64-wide map occur in no model, have not been measured and stay
+// on the per-tap path.
+bool rows_auto(int B, int A, int WO) {
+  return WO == RW && B <= 128 && A <= 256;
+}
+
+// P2PVG_WGRAD_ROWS=pertap keeps auto off the row-order kernel (A/B timing;
+// the results are bitwise the same either way)
+bool g_wgrad_rows = true;
+
+enum WgradPath { WG_PER_TAP = 0, WG_STRIP = 1, WG_ROWS = 2 };
+
+// Path of a 3x3 stride-1 PAD == 0 wgrad over a zero-ringed X (H >= HO + 2,
+// W >= WO + 2) with more than 3 input channels. taps: 0 per-tap, 1 strip
+// kernel, 2 row-order kernel (3 / 4: with 64x64 / 32x64 tiles forced), -1
+// auto. A required kernel whose geometry is not eligible raises.
+WgradPath wgrad_k3_path(int B, int A, int A1, int HO, int WO, int yring,
+                        long taps) {
+  TORCH_CHECK(taps >= -1 && taps <= 4, "wgrad: taps must be -1..4");
+  const bool pow2 = HO > 0 && WO > 0 && ((HO * WO) & (HO * WO - 1)) == 0 &&
+                    (WO & (WO - 1)) == 0;
+  const bool ch_ok = B > 0 && A1 > 0 && B % 64 == 0 && A1 % 64 == 0 &&
+                     A % 64 == 0 && yring >= 0 && pow2;
+  const bool strip_ok = ch_ok && WO >= TPW && HO >= 4;
+  const bool rows_ok = ch_ok && WO == RW;
+  TORCH_CHECK(taps != 1 || strip_ok,
+              "wgrad: taps path required but the geometry is not eligible");
+  TORCH_CHECK(taps < 2 || rows_ok,
+              "wgrad: row-order taps path required but the geometry is not "
+              "eligible");
+  if (taps >= 2) return WG_ROWS;
+  if (taps == 1) return WG_STRIP;
+  if (taps == 0) return WG_PER_TAP;
+  if (rows_ok && g_wgrad_rows && rows_auto(B, A, WO)) return WG_ROWS;
+  if (strip_ok && taps_auto(B, A, WO)) return WG_STRIP;
+  return WG_PER_TAP;
 }
 
 // fixed-order combine of the 3x3 slab planes (or accumulate into `acc`)
@@ -1096,6 +1422,25 @@ torch::Tensor wgrad_finish(torch::Tensor ws, c10::optional<torch::Tensor> acc,
 
 }  // namespace
 
+// auto's use of the row-order kernel on or off (off: P2PVG_WGRAD_ROWS=pertap)
+void set_wgrad_rows(bool on) { g_wgrad_rows = on; }
+bool wgrad_rows() { return g_wgrad_rows; }
+
+// Host only: the path conv2d_nhwc_wgrad takes for a 3x3 stride-1 PAD == 0
+// call over a zero-ringed X of A channels (A1 of them in the first source)
+// and a Y of B channels on an HO x WO map: "per_tap", "taps_strip" or
+// "taps_rows". The three give the same bits wherever auto picks among them,
+// so this is how a test sees the choice.
+std::string conv2d_wgrad_path(long B, long A, long A1, long HO, long WO,
+                              long yring, long taps) {
+  switch (wgrad_k3_path((int)B, (int)A, (int)A1, (int)HO, (int)WO, (int)yring,
+                        taps)) {
+    case WG_ROWS: return "taps_rows";
+    case WG_STRIP: return "taps_strip";
+    default: return "per_tap";
+  }
+}
+
 // Y: channels_last (N,B,HO,WO) bf16; X: channels_last (N,A,H,W) bf16.
 // Returns dW (B, R, S, A) fp32. splitp<=0 -> auto. When `acc` is given it
 // must be an fp32 tensor whose dense layout is (B,R,S,A) (e.g. the conv
@@ -1104,7 +1449,9 @@ torch::Tensor wgrad_finish(torch::Tensor ws, c10::optional<torch::Tensor> acc,
 // accumulation adds entirely (the ~29 uses per weight per step land here).
 // thin: -1 picks the thin-channel path when the geometry allows it, 0 never
 // takes it, 1 requires it (raises otherwise). taps: the same three values for
-// the single-pass all-taps 3x3 kernel.
+// the single-pass all-taps 3x3 strip kernel; 2 requires the row-order
+// all-taps kernel (64-wide maps; 3 / 4 the same with 64x64 / 32x64 tiles
+// forced, where 2 picks the tile by CU fill).
 torch::Tensor conv2d_nhwc_wgrad(torch::Tensor Y, torch::Tensor X, long R,
                                 long S, long stride, long pad, long splitp,
                                 c10::optional<torch::Tensor> acc, long yring,
@@ -1149,16 +1496,19 @@ torch::Tensor conv2d_nhwc_wgrad(torch::Tensor Y, torch::Tensor X, long R,
               "wgrad: thin path required but the geometry is not eligible");
   const bool use_thin = thin_ok && thin != 0;
 
-  // single-pass all-taps path: 3x3 stride 1 over a zero-ringed X, 64-aligned
-  // channels (each X part), 32-column strips and two-row chunks
-  const bool taps_ok =
-      !use_thin && R == 3 && S == 3 && stride == 1 && pad == 0 && yring >= 0 &&
-      B % 64 == 0 && A1 % 64 == 0 && A % 64 == 0 && pow2 && WO >= TPW &&
-      HO >= 4 && H >= HO + 2 && W >= WO + 2;
-  TORCH_CHECK(taps != 1 || taps_ok,
+  // single-pass all-taps paths: 3x3 stride 1 over a zero-ringed X, 64-aligned
+  // channels (each X part); the strip kernel (32-column strips, two-row
+  // chunks) or, on 64-wide maps, the row-order kernel (one-row chunks)
+  const bool k3_ringed = !use_thin && R == 3 && S == 3 && stride == 1 &&
+                         pad == 0 && H >= HO + 2 && W >= WO + 2;
+  TORCH_CHECK(taps >= -1 && taps <= 4, "wgrad: taps must be -1..4");
+  TORCH_CHECK(taps < 1 || k3_ringed,
               "wgrad: taps path required but the geometry is not eligible");
-  const bool use_taps =
-      taps_ok && (taps == 1 || (taps != 0 && taps_auto(B, A, WO)));
+  const WgradPath path =
+      k3_ringed ? wgrad_k3_path(B, A, A1, HO, WO, (int)yring, taps)
+                : WG_PER_TAP;
+  const bool use_taps = path == WG_STRIP;
+  const bool use_rows = path == WG_ROWS;
 
   int sp = (int)splitp;
   if (sp <= 0) {
@@ -1171,6 +1521,44 @@ torch::Tensor conv2d_nhwc_wgrad(torch::Tensor Y, torch::Tensor X, long R,
   const int p_per_slab =
       ceil_div(ceil_div(p_total, sp), PCH) * PCH;  // chunk-aligned
   sp = ceil_div(p_total, p_per_slab);
+
+  if (use_rows) {
+    // per-tap slabs (whole rows: p_per_slab is a multiple of the 64-pixel
+    // row) and the per-tap combine; a chunk is one output row, summed in the
+    // per-tap kernel's order, so the result is bitwise the per-tap path's.
+    // Half tiles when full tiles would leave more than half the CUs idle.
+    int ho_sh = 0;
+    while ((1 << ho_sh) < HO) ++ho_sh;
+    const int tiles64 = (B / 64) * (A / 64);
+    const int cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+    const bool half = taps == 4 || (taps != 3 && 2 * tiles64 * sp <= cus);
+    auto rws = torch::empty({sp, B, 3, 3, A},
+                            Y.options().dtype(torch::kFloat32));
+    auto rstream = at::cuda::getCurrentCUDAStream();
+#define WGRAD_RLAUNCH(BB)                                                     \
+  do {                                                                        \
+    static bool cfg = false;                                                  \
+    if (!cfg) {                                                               \
+      (void)hipFuncSetAttribute(                                              \
+          (const void*)&conv2d_wgrad_rows_kernel<BB>,                         \
+          hipFuncAttributeMaxDynamicSharedMemorySize, RowsCfg<BB>::LDS);      \
+      cfg = true;                                                             \
+    }                                                                         \
+    hipLaunchKernelGGL(                                                       \
+        (conv2d_wgrad_rows_kernel<BB>), dim3((B / BB) * (A / 64), 1, sp),     \
+        dim3(THREADS), RowsCfg<BB>::LDS, rstream,                             \
+        reinterpret_cast<const __bf16*>(Y.data_ptr()),                        \
+        reinterpret_cast<const __bf16*>(X.data_ptr()),                        \
+        X2.has_value() ? reinterpret_cast<const __bf16*>(X2->data_ptr())      \
+                       : nullptr,                                             \
+        rws.data_ptr<float>(), HO, B, H, W, A, A1, (int)yring,                \
+        p_total / PCH, p_per_slab / PCH, ho_sh);                              \
+  } while (0)
+    if (half) WGRAD_RLAUNCH(32);
+    else WGRAD_RLAUNCH(64);
+#undef WGRAD_RLAUNCH
+    return wgrad_finish(rws, acc, sp, B, A, E, rstream);
+  }
 
   if (use_taps) {
     // the slabs are those of the per-tap path (same sp rule, same 64-pixel

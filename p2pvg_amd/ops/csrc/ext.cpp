@@ -84,6 +84,10 @@ torch::Tensor conv2d_nhwc_wgrad(torch::Tensor Y, torch::Tensor X, long R,
                                 c10::optional<torch::Tensor> acc, long yring,
                                 c10::optional<torch::Tensor> X2, long thin,
                                 long taps);
+std::string conv2d_wgrad_path(long B, long A, long A1, long HO, long WO,
+                              long yring, long taps);
+void set_wgrad_rows(bool on);
+bool wgrad_rows();
 std::vector<torch::Tensor> maxpool2x2_fwd(torch::Tensor in, long ri, long ro);
 torch::Tensor maxpool2x2_bwd(torch::Tensor gout, torch::Tensor idx, long H,
                              long W, long ri, long ro);
@@ -161,12 +165,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "NHWC wgrad, split-K over pixel slabs (gfx950 MFMA, deterministic); "
         "acc: fp32 dense (B,R,S,A)-layout tensor to accumulate into; "
         "thin: -1 auto, 0 never, 1 require the thin-channel path; "
-        "taps: the same for the single-pass all-taps 3x3 path",
+        "taps: the same for the single-pass all-taps 3x3 strip kernel, 2 "
+        "requires the row-order all-taps kernel (3 / 4: 64x64 / 32x64 tiles)",
         pybind11::arg("Y"), pybind11::arg("X"), pybind11::arg("R"),
         pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"),
         pybind11::arg("splitp") = 0, pybind11::arg("acc") = c10::nullopt,
         pybind11::arg("yring") = 0, pybind11::arg("X2") = c10::nullopt,
         pybind11::arg("thin") = -1, pybind11::arg("taps") = -1);
+  m.def("conv2d_wgrad_path", &conv2d_wgrad_path,
+        "host only: path of a 3x3 s1 pad-0 ringed-X wgrad call: 'per_tap', "
+        "'taps_strip' or 'taps_rows'",
+        pybind11::arg("B"), pybind11::arg("A"), pybind11::arg("A1"),
+        pybind11::arg("HO"), pybind11::arg("WO"), pybind11::arg("yring"),
+        pybind11::arg("taps") = -1);
+  m.def("set_wgrad_rows", &set_wgrad_rows,
+        "auto may use the row-order all-taps wgrad kernel (default true); "
+        "false keeps those classes on the per-tap path (bitwise the same)",
+        pybind11::arg("on"));
+  m.def("wgrad_rows", &wgrad_rows, "current row-order wgrad auto mode");
   m.def("maxpool2x2_fwd", &maxpool2x2_fwd, "NHWC 2x2/s2 maxpool fwd (gfx950)",
         pybind11::arg("in"), pybind11::arg("ri") = 0, pybind11::arg("ro") = 0);
   m.def("maxpool2x2_bwd", &maxpool2x2_bwd, "NHWC 2x2/s2 maxpool bwd (gfx950)",

@@ -1,13 +1,18 @@
 #!/usr/bin/env python
-"""A/B the single-pass all-taps 3x3 wgrad against the per-tap kernel.
+"""A/B the single-pass all-taps 3x3 wgrad kernels against the per-tap kernel.
 
-Run on a GPU box: python scripts/prof_wgrad.py [batch]
+Run on a GPU box: python scripts/prof_wgrad.py [batch] [w64]
 For every vgg k3 wgrad shape (training form: X zero-ringed with pad=0, Y with
-a ring of 1; the decoder's concat layers as dual-X pairs) prints the per-tap
-pair time (taps=0), the all-taps pair time (taps=1, where eligible), their
-ratio, the TF and staged-bytes rate of the faster one's column and the max
-error of both against fp32 torch.nn.grad.conv2d_weight. "Pair" is kernel plus
-combine: the whole conv2d_nhwc_wgrad call.
+a ring of 1; the decoder's concat layers as dual-X pairs) prints the pair time
+of the per-tap path (taps=0), of the strip all-taps kernel (taps=1) and of the
+row-order all-taps kernel with 64x64 and with 32x64 tiles (taps=3, taps=4;
+64-wide maps only), each where eligible. "Pair" is kernel plus combine: the
+whole conv2d_nhwc_wgrad call, with the per-tap path's slabs in every column.
+Each time is the mean of REPS timings of 20 calls, followed by their max-min
+spread; "ratio" is per-tap over the fastest all-taps column, TF and staged
+TB/s are that column's. "bits" tells whether that column's result is bitwise
+the per-tap one. The argument w64 keeps only the 64-wide shapes, the two of
+the 64-pixel model and those the 128-pixel model adds.
 """
 import sys
 
@@ -19,7 +24,11 @@ from p2pvg_amd.ops import _hip_ext_loader  # noqa: E402
 
 CL = torch.channels_last
 ext = _hip_ext_loader.load()
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 128
+ARGS = sys.argv[1:]
+W64 = "w64" in ARGS
+ARGS = [a for a in ARGS if a != "w64"]
+N = int(ARGS[0]) if ARGS else 128
+REPS = 3
 
 # tag, A (X channels; a tuple is a dual-X pair), spatial, B (Y channels)
 SHAPES = [
@@ -36,20 +45,33 @@ SHAPES = [
     ("vgg d5cat", (64, 64), 64, 64),
     ("vgg upc4.1", 128, 32, 64),
 ]
+# the 64-wide classes the 128-pixel model reaches one level down
+SHAPES_128 = [
+    ("v128 c2.0", 64, 64, 128),
+    ("v128 c2.1", 128, 64, 128),
+    ("v128 d4cat", (128, 128), 64, 128),
+    ("v128 upc4.1", 128, 64, 64),
+]
+if W64:
+    SHAPES = [s for s in SHAPES if s[2] == 64] + SHAPES_128
 
 
 def timeit(f, n=20):
+    """(mean, max - min) in us over REPS timings of n calls."""
     for _ in range(3):
         f()
     torch.cuda.synchronize()
-    s = torch.cuda.Event(enable_timing=True)
-    e = torch.cuda.Event(enable_timing=True)
-    s.record()
-    for _ in range(n):
-        f()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / n * 1000
+    ts = []
+    for _ in range(REPS):
+        s = torch.cuda.Event(enable_timing=True)
+        e = torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(n):
+            f()
+        e.record()
+        torch.cuda.synchronize()
+        ts.append(s.elapsed_time(e) / n * 1000)
+    return sum(ts) / len(ts), max(ts) - min(ts)
 
 
 def reference(x, g, b, a):
@@ -66,9 +88,15 @@ def tile(ch):
     return 128 if ch % 128 == 0 else 64
 
 
+def cell(t):
+    return f"{t[0]:>7.1f} ±{t[1]:<5.1f}" if t else f"{'-':>7} {'':<6}"
+
+
+MODES = [(1, "strip"), (3, "rows64"), (4, "rows32")]
 print(f"batch {N}")
-print(f"{'shape':<10} {'B':>4} {'A':>9} {'hw':>3} {'per-tap us':>10} "
-      f"{'taps us':>8} {'ratio':>6} {'TF':>5} {'staged TB/s':>11} "
+print(f"{'shape':<11} {'B':>4} {'A':>10} {'hw':>3} {'per-tap us':>14} "
+      + " ".join(f"{name + ' us':>14}" for _, name in MODES)
+      + f" {'best':>6} {'ratio':>6} {'TF':>5} {'staged TB/s':>11} {'bits':>5} "
       f"{'err old':>9} {'err new':>9} {'scale':>8}")
 for tag, a_spec, h, b in SHAPES:
     parts = a_spec if isinstance(a_spec, tuple) else (a_spec,)
@@ -91,27 +119,35 @@ for tag, a_spec, h, b in SHAPES:
     def err(ws):
         return (ws.permute(0, 3, 1, 2) - ref).abs().max().item()
 
-    e_old = err(call(0))
+    w_old = call(0)
+    e_old = err(w_old)
     t_old = timeit(lambda: call(0))
-    try:
-        e_new = err(call(1))
-    except RuntimeError:
-        e_new = None
+    times, outs = {}, {}
+    for taps, name in MODES:
+        try:
+            outs[name] = call(taps)
+        except RuntimeError:
+            times[name] = None
+            continue
+        times[name] = timeit(lambda: call(taps))
     flops = 2.0 * N * h * h * b * a * 9
     ybytes = gp.numel() * 2
     xbytes = sum(t.numel() for t in xs) * 2
-    if e_new is None:
+    head = (f"{tag:<11} {b:>4} {str(a_spec):>10} {h:>3} {cell(t_old)} "
+            + " ".join(cell(times[name]) for _, name in MODES))
+    if not outs:
         staged = 9 * (a // tile(a) * ybytes + b // tile(b) * xbytes)
-        print(f"{tag:<10} {b:>4} {str(a_spec):>9} {h:>3} {t_old:>10.1f} "
-              f"{'-':>8} {'-':>6} {flops / t_old / 1e6:>5.0f} "
-              f"{staged / t_old / 1e6:>11.2f} {e_old:>9.2e} {'-':>9} "
-              f"{scale:>8.1f}")
+        print(f"{head} {'-':>6} {'-':>6} {flops / t_old[0] / 1e6:>5.0f} "
+              f"{staged / t_old[0] / 1e6:>11.2f} {'-':>5} {e_old:>9.2e} "
+              f"{'-':>9} {scale:>8.1f}")
         continue
-    t_new = timeit(lambda: call(1))
+    best = min(outs, key=lambda k: times[k][0])
+    t_new = times[best][0]
     # every Y pixel once per a-tile, every X row as three shifted images
-    # once per b-tile
-    staged = a // 64 * ybytes + b // 64 * 3 * xbytes
-    print(f"{tag:<10} {b:>4} {str(a_spec):>9} {h:>3} {t_old:>10.1f} "
-          f"{t_new:>8.1f} {t_old / t_new:>6.2f} {flops / t_new / 1e6:>5.0f} "
-          f"{staged / t_new / 1e6:>11.2f} {e_old:>9.2e} {e_new:>9.2e} "
-          f"{scale:>8.1f}")
+    # once per b-tile (32-row b-tiles for rows32)
+    btile = 32 if best == "rows32" else 64
+    staged = a // 64 * ybytes + b // btile * 3 * xbytes
+    same = "same" if torch.equal(outs[best], w_old) else "differ"
+    print(f"{head} {best:>6} {t_old[0] / t_new:>6.2f} "
+          f"{flops / t_new / 1e6:>5.0f} {staged / t_new / 1e6:>11.2f} "
+          f"{same:>5} {e_old:>9.2e} {err(outs[best]):>9.2e} {scale:>8.1f}")
