@@ -27,7 +27,15 @@ def load():
         if rows not in ("rows", "pertap"):
             raise ValueError(
                 f"P2PVG_WGRAD_ROWS must be 'rows' or 'pertap', got {rows!r}")
+        # P2PVG_WGRAD_NARROW=narrow|pertap, likewise, for the 16-wide 3x3
+        # weight-gradient classes and the narrow all-taps kernel.
+        narrow = os.environ.get("P2PVG_WGRAD_NARROW", "narrow")
+        if narrow not in ("narrow", "pertap"):
+            raise ValueError(
+                "P2PVG_WGRAD_NARROW must be 'narrow' or 'pertap', "
+                f"got {narrow!r}")
         _C.set_bn_tail_fused(tail == "fused")
         _C.set_wgrad_rows(rows == "rows")
+        _C.set_wgrad_narrow(narrow == "narrow")
         _tail_env_applied = True
     return _C

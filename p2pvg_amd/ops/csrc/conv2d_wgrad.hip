@@ -1298,6 +1298,266 @@ __global__ __launch_bounds__(THREADS) void conv2d_wgrad_rows_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------
+// All-taps 3x3 wgrad for 16-wide maps: the strip kernel above with 16-pixel
+// row images and four-row chunks, summed in exactly the per-tap kernel's
+// order. (stride 1, PAD == 0 over a zero-ringed X, WO == 16, HO a power of
+// two >= 8, B, A1 and A multiples of 64, any yring.)
+//
+// What fixes the bits. A chunk is 64 consecutive output pixels, which on a
+// 16-wide map is four output rows of one image (HO is a multiple of 4, so a
+// chunk never crosses an image); its two MFMA K-steps are pixels 0-31 (rows
+// 0-1) and 32-63 (rows 2-3), lane group g = lane>>4 holding pixels
+// g*8..g*8+7 of the step: groups 0-1 the two halves of the step's first row,
+// groups 2-3 those of its second. The slabs are the per-tap path's (any chunk
+// may start one, also mid-image) and each element has one accumulator chain
+// per slab. Tile shape, wave layout and LDS layout do not enter the sums.
+//
+// X side: each input row is staged ONCE as three column-shifted
+// [16 pix][64 ch] subtiled images (2 KB each, 6 KB per row). Tap (r,s) of
+// output row ho is the aligned tr16 read of image s of input row ho + r; an
+// 8-pixel run is two whole pixel groups of one row image. A chunk reads six
+// input rows, of which the chunk before it staged two: a steady chunk stages
+// four rows plus one Y image, 24 KB + 8 KB against 9 x 32 KB for the per-tap
+// kernel's 128x128 tile. The first chunk of a slab and of every image is a
+// restart and stages six rows.
+//
+// Ring: when chunk k is staged, chunk k-2 is being computed (6 rows) and
+// chunk k-1 is in flight (4 or 6 new rows); an image is at least two chunks,
+// so at most one of k-1, k is a restart: 6 + 4 + 6 = 16 row slots, handed out
+// by a running counter. Y rotates through 3 buffers.
+//
+// Tiles. BTB = 64: a 64(b) x 64(a) tile, 4 waves, 120 KB of LDS. BTB = 128: a
+// 128(b) x 64(a) tile, 8 waves, the same row ring under a 16 KB Y image (144
+// KB): the X rows are staged once for twice the b-channels, 24 + 16 KB per
+// chunk against 2 x 32 KB, and a CU holds 8 waves instead of 4. It is taken
+// wherever B is a multiple of 128 (1.28-1.44x over the 64x64 tile on every
+// class of profiles/prof_wgrad_narrow_b512.txt).
+//
+// vmcnt. At the top of iteration t the only calls a wave issued after
+// stage(t) are those of stage(t+1) (stage(t+2) follows the barrier): G = 8 / 5
+// (BTB 64 / 128) when chunk t+1 is steady, GR = 11 / 7 when it is a restart,
+// none when chunk t is the slab's last. Every wave issues the same number of
+// calls per stage. Loads retire in order, so waiting for exactly that count
+// retires stage(t) whatever stage(t) itself counted.
+//
+// Waves: (BTB/32) x 2 over the tile, each 32(b) x 32(a) x 9 taps = 36
+// fragments (144 accumulator registers), as in the strip kernel. A K-step
+// spans two input rows per tap, so the transpose-read base is per lane group:
+// a lane holds the addresses of rows (g>>1)..(g>>1)+4 of the chunk's six,
+// which may sit in non-adjacent slots where the ring wraps.
+
+constexpr int NW = 16;                  // map width = pixels per row image
+constexpr int NW_IMG = NW * 64 * 2;     // one shifted row image, 2 KB
+constexpr int NW_ROW = 3 * NW_IMG;      // the three shifts of one row, 6 KB
+constexpr int NW_NR = 16;               // row ring slots
+constexpr int NW_RU = NW_ROW / 1024;    // 1 KB glds units per row: 6
+
+template <int BTB>
+struct NarrowCfg {
+  static constexpr int WAVES = BTB / 16;             // 4 / 8
+  static constexpr int NT = WAVES * 64;              // threads per block
+  static constexpr int YIMG = PCH * BTB * 2;         // Y image of one chunk
+  static constexpr int YC = YIMG / 1024 / WAVES;     // glds calls per wave (Y)
+  static constexpr int XS = 4 * NW_RU / WAVES;       // X calls, steady: 6 / 3
+  static constexpr int XR = (6 * NW_RU + WAVES - 1) / WAVES;  // restart: 9 / 5
+  static constexpr int G = XS + YC;                  // steady chunk: 8 / 5
+  static constexpr int GR = XR + YC;                 // restart chunk: 11 / 7
+  static constexpr int LDS = NW_NR * NW_ROW + 3 * YIMG;  // 120 / 144 KB
+  static constexpr int YHALF = (BTB / 16) * 128;  // next pixel-group row of Y
+};
+
+// the X fragments of tap TP (image TP % 3 of the row at `ra`)
+template <int TP>
+__device__ __forceinline__ void narrow_issue_x(unsigned ra, u16x4 (&lo)[2],
+                                               u16x4 (&hi)[2]) {
+  constexpr int off = (TP % 3) * NW_IMG;
+  tr16_issue_off<off, 512>(ra, lo[0], hi[0]);
+  tr16_issue_off<off + 128, 512>(ra, lo[1], hi[1]);
+}
+
+// one 32-pixel K-step (two output rows) of a chunk for all nine taps, the
+// reads of tap tp+1 in flight while tap tp multiplies (cf. rows_kstep).
+// rowa[i]: this lane's input row i of the step, i.e. tap row r reads rowa[r]
+template <int BTB, int KK>
+__device__ __forceinline__ void narrow_kstep(unsigned ya,
+                                             const unsigned* rowa,
+                                             f32x4 (&acc)[9][2][2]) {
+  constexpr int YHALF = NarrowCfg<BTB>::YHALF;
+  constexpr int yk = KK * 8 * YHALF;  // pixels KK*32.. of the Y image
+  u16x4 ylo[2], yhi[2], xlo[2][2], xhi[2][2];
+  tr16_issue_off<yk, YHALF>(ya, ylo[0], yhi[0]);
+  tr16_issue_off<yk + 128, YHALF>(ya, ylo[1], yhi[1]);
+  narrow_issue_x<0>(rowa[0], xlo[0], xhi[0]);
+#define NW_TAP(TP)                                                          \
+  narrow_issue_x<(TP) + 1>(rowa[((TP) + 1) / 3], xlo[((TP) + 1) & 1],       \
+                           xhi[((TP) + 1) & 1]);                            \
+  if ((TP) == 0) rows_wait<4>(ylo, yhi);                                    \
+  rows_wait<4>(xlo[(TP) & 1], xhi[(TP) & 1]);                               \
+  rows_mma<2>(acc[TP], ylo, yhi, xlo[(TP) & 1], xhi[(TP) & 1]);
+  NW_TAP(0) NW_TAP(1) NW_TAP(2) NW_TAP(3) NW_TAP(4) NW_TAP(5) NW_TAP(6)
+  NW_TAP(7)
+#undef NW_TAP
+  rows_wait<0>(xlo[0], xhi[0]);
+  rows_mma<2>(acc[8], ylo, yhi, xlo[0], xhi[0]);
+}
+
+template <int BTB>
+__global__ __launch_bounds__(NarrowCfg<BTB>::NT) void
+conv2d_wgrad_narrow_kernel(
+    const __bf16* __restrict__ Y, const __bf16* __restrict__ X,
+    const __bf16* __restrict__ X2, float* __restrict__ ws, int HO, int B,
+    int H, int W, int A, int A1, int yring, int nchunks, int cps, int img_sh) {
+  using C = NarrowCfg<BTB>;
+  extern __shared__ __align__(16) char nlds[];
+  char* const ybufs = nlds + NW_NR * NW_ROW;
+
+  const int at_blocks = A >> 6;
+  const int b0 = (blockIdx.x / at_blocks) * BTB;
+  const int a0 = (blockIdx.x % at_blocks) * 64;
+  const int c_begin = blockIdx.z * cps;
+  const int nch = min(c_begin + cps, nchunks) - c_begin;
+
+  const int tid = threadIdx.x;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63;
+  const int wm = (wid >> 1) * 32;
+  const int wn = (wid & 1) * 32;
+  const int HOp = HO + 2 * yring;
+  const int WOp = NW + 2 * yring;
+
+  // dual-X: the 64-wide a-tile lies wholly in one source (A1 % 64 == 0)
+  const bool second = X2 != nullptr && a0 >= A1;
+  const __bf16* xsrc = second ? X2 + (a0 - A1) : X + a0;
+  const int as = X2 == nullptr ? A : (second ? A - A1 : A1);
+  const __bf16* ysrc = Y + b0;
+
+  // A stage of nr rows is nr * NW_RU glds units of 1 KB, dealt to the waves
+  // in order: unit u is row u/6, image (u%6)/2, pixel half u&1. The 36 units
+  // of a restart do not divide by 8 waves: the last wave's calls past the end
+  // wrap to units 0..3 and write the bytes wave 0 writes there once more,
+  // which keeps the call count the same in every wave.
+  auto unit_of = [&](int i, bool fresh) {
+    const int u = wid * (fresh ? C::XR : C::XS) + i;
+    return u >= 6 * NW_RU ? u - 6 * NW_RU : u;
+  };
+  // per-lane staging offsets (elements), fixed for the whole kernel
+  int xs_off[C::XS], xr_off[C::XR], yl_off[C::YC];
+  auto unit_off = [&](int u) {
+    const int row = u / NW_RU;
+    const int q = u - row * NW_RU;
+    int pixl, ch0;
+    glds_decode((q & 1) * 64 + lane, 2, pixl, ch0);
+    return (row * W + pixl + (q >> 1)) * as + ch0;  // column pixl + s <= 17
+  };
+#pragma unroll
+  for (int i = 0; i < C::XS; ++i) xs_off[i] = unit_off(unit_of(i, false));
+#pragma unroll
+  for (int i = 0; i < C::XR; ++i) xr_off[i] = unit_off(unit_of(i, true));
+#pragma unroll
+  for (int i = 0; i < C::YC; ++i) {
+    int pixl, ch0;
+    glds_decode((wid * C::YC + i) * 64 + lane, BTB == 128 ? 3 : 2, pixl, ch0);
+    yl_off[i] = ((pixl >> 4) * WOp + (pixl & (NW - 1))) * B + ch0;
+  }
+
+  const int img_mask = (1 << img_sh) - 1;  // chunks per image - 1
+  auto restart = [&](int c) { return c == c_begin || (c & img_mask) == 0; };
+
+  int sctr = 0;  // ring slot the next staged row goes to
+  // LDS address of unit u of a stage whose first row goes to slot sctr
+  auto unit_lds = [&](int u) {
+    const int row = u / NW_RU;
+    return nlds + ((sctr + row) & (NW_NR - 1)) * NW_ROW +
+           (u - row * NW_RU) * 1024;
+  };
+  auto stage = [&](int c, int ybuf) {
+    const int n = c >> img_sh;
+    const int ho0 = (c & img_mask) * 4;
+    const bool fresh = restart(c);
+    const int hi0 = fresh ? ho0 : ho0 + 2;
+    const __bf16* rb = xsrc + (long)(n * H + hi0) * W * as;
+    if (fresh) {
+#pragma unroll
+      for (int i = 0; i < C::XR; ++i)
+        wglds16(rb + xr_off[i], unit_lds(unit_of(i, true)));
+    } else {
+#pragma unroll
+      for (int i = 0; i < C::XS; ++i)
+        wglds16(rb + xs_off[i], unit_lds(unit_of(i, false)));
+    }
+    sctr = (sctr + (fresh ? 6 : 4)) & (NW_NR - 1);
+    const __bf16* yb =
+        ysrc + (((long)n * HOp + ho0 + yring) * WOp + yring) * B;
+    char* l = ybufs + ybuf * C::YIMG + wid * C::YC * 1024;
+#pragma unroll
+    for (int i = 0; i < C::YC; ++i) wglds16(yb + yl_off[i], l + i * 1024);
+  };
+
+  f32x4 acc[9][2][2];
+#pragma unroll
+  for (int tp = 0; tp < 9; ++tp)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc[tp][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // per-lane tr16 bases. Y image: pixel run (lane>>4)*8 = two pixel-group
+  // rows. X row image: run ((lane>>4)&1)*8 of the row lane>>5 rows down.
+  const int grow = lane >> 5;
+  const unsigned yrd = (unsigned)(unsigned long long)ybufs +
+                       (unsigned)((lane >> 4) * 2 * C::YHALF +
+                                  (lane & 15) * 8 + (wm >> 4) * 128);
+  const unsigned xrd = (unsigned)(unsigned long long)nlds +
+                       (unsigned)(((lane >> 4) & 1) * 2 * 512 +
+                                  (lane & 15) * 8 + (wn >> 4) * 128);
+
+  int cctr = 0;  // ring slot of the first row the next restart chunk reads
+  auto compute = [&](int c, int ybuf) {
+    const bool fresh = restart(c);
+    const int slot0 = fresh ? cctr : (cctr - 2) & (NW_NR - 1);
+    cctr = (cctr + (fresh ? 6 : 4)) & (NW_NR - 1);
+    // rows grow..grow+4 of the chunk's six
+    unsigned rowa[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j)
+      rowa[j] = xrd +
+                (unsigned)(((slot0 + grow + j) & (NW_NR - 1)) * NW_ROW);
+    const unsigned ya = yrd + (unsigned)(ybuf * C::YIMG);
+    narrow_kstep<BTB, 0>(ya, rowa, acc);
+    narrow_kstep<BTB, 1>(ya, rowa + 2, acc);
+  };
+
+  if (nch > 0) stage(c_begin, 0);
+  if (nch > 1) stage(c_begin + 1, 1);
+  int ybuf = 0;
+  for (int t = 0; t < nch; ++t) {
+    if (t + 1 >= nch) wwaitcnt_vm<0>();
+    else if (restart(c_begin + t + 1)) wwaitcnt_vm<C::GR>();
+    else wwaitcnt_vm<C::G>();
+    wbarrier_mem();
+    // buffer (t+2)%3 and the slots it takes were last read by chunk t-1
+    if (t + 2 < nch) stage(c_begin + t + 2, ybuf >= 1 ? ybuf - 1 : 2);
+    compute(c_begin + t, ybuf);
+    ybuf = ybuf == 2 ? 0 : ybuf + 1;
+  }
+
+  float* slab = ws + (long)blockIdx.z * B * 9 * A;
+#pragma unroll
+  for (int tp = 0; tp < 9; ++tp)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int a = a0 + wn + j * 16 + (lane & 15);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int b = b0 + wm + i * 16 + (lane >> 4) * 4 + v;
+          slab[((long)b * 9 + tp) * A + a] = acc[tp][i][j][v];
+        }
+    }
+}
+
 // out[e] (+)= sum over slabs ws[z][e] — serial over z (deterministic).
 __global__ __launch_bounds__(256) void wgrad_combine_kernel(
     const float* __restrict__ ws, float* __restrict__ out, int sp, long E,
@@ -1366,35 +1626,60 @@ bool rows_auto(int B, int A, int WO) {
   return WO == RW && B <= 128 && A <= 256;
 }
 
+// (B, A) classes of 16-wide maps auto sends to the narrow all-taps kernel:
+// those whose per-call time (kernel plus combine, per-tap slabs, batch 512)
+// beat the per-tap path by more than the run-to-run spread in
+// profiles/prof_wgrad_narrow_b512.txt, all with 128x64 tiles: the four of the
+// 64-pixel model (c3.0 256x128, c3.1 256x256, upc3.0 256x(256+256), upc3.2
+// 128x256: 2.11x-2.30x) and the four the 128-pixel model reaches (B 512 or
+// 256, A 256 to 512+512: 2.11x-2.44x). Anything else, the 64x64 tile
+// included, has not been measured against per-tap under auto's rule and
+// stays on the per-tap path.
+bool narrow_auto(int B, int A, int WO) {
+  if (WO != NW) return false;
+  if (B == 128) return A == 256;
+  return (B == 256 || B == 512) && 2 * A >= B && A <= 2 * B;
+}
+
 // P2PVG_WGRAD_ROWS=pertap keeps auto off the row-order kernel (A/B timing;
 // the results are bitwise the same either way)
 bool g_wgrad_rows = true;
+// P2PVG_WGRAD_NARROW=pertap: the same for the 16-wide narrow kernel
+bool g_wgrad_narrow = true;
 
-enum WgradPath { WG_PER_TAP = 0, WG_STRIP = 1, WG_ROWS = 2 };
+enum WgradPath { WG_PER_TAP = 0, WG_STRIP = 1, WG_ROWS = 2, WG_NARROW = 3 };
 
 // Path of a 3x3 stride-1 PAD == 0 wgrad over a zero-ringed X (H >= HO + 2,
 // W >= WO + 2) with more than 3 input channels. taps: 0 per-tap, 1 strip
-// kernel, 2 row-order kernel (3 / 4: with 64x64 / 32x64 tiles forced), -1
+// kernel, 2 row-order kernel (3 / 4: with 64x64 / 32x64 tiles forced), 5
+// narrow kernel (16-wide maps; 6 / 7: with 64x64 / 128x64 tiles forced), -1
 // auto. A required kernel whose geometry is not eligible raises.
 WgradPath wgrad_k3_path(int B, int A, int A1, int HO, int WO, int yring,
                         long taps) {
-  TORCH_CHECK(taps >= -1 && taps <= 4, "wgrad: taps must be -1..4");
+  TORCH_CHECK(taps >= -1 && taps <= 7, "wgrad: taps must be -1..7");
   const bool pow2 = HO > 0 && WO > 0 && ((HO * WO) & (HO * WO - 1)) == 0 &&
                     (WO & (WO - 1)) == 0;
   const bool ch_ok = B > 0 && A1 > 0 && B % 64 == 0 && A1 % 64 == 0 &&
                      A % 64 == 0 && yring >= 0 && pow2;
   const bool strip_ok = ch_ok && WO >= TPW && HO >= 4;
   const bool rows_ok = ch_ok && WO == RW;
+  // an image of at least two chunks: what the 16-slot ring is sized for
+  const bool narrow_ok = ch_ok && WO == NW && HO >= 8;
   TORCH_CHECK(taps != 1 || strip_ok,
               "wgrad: taps path required but the geometry is not eligible");
-  TORCH_CHECK(taps < 2 || rows_ok,
+  TORCH_CHECK(taps < 2 || taps > 4 || rows_ok,
               "wgrad: row-order taps path required but the geometry is not "
               "eligible");
+  TORCH_CHECK(taps < 5 || (narrow_ok && (taps != 7 || B % 128 == 0)),
+              "wgrad: narrow taps path required but the geometry is not "
+              "eligible");
+  if (taps >= 5) return WG_NARROW;
   if (taps >= 2) return WG_ROWS;
   if (taps == 1) return WG_STRIP;
   if (taps == 0) return WG_PER_TAP;
   if (rows_ok && g_wgrad_rows && rows_auto(B, A, WO)) return WG_ROWS;
   if (strip_ok && taps_auto(B, A, WO)) return WG_STRIP;
+  if (narrow_ok && g_wgrad_narrow && narrow_auto(B, A, WO)) return WG_NARROW;
   return WG_PER_TAP;
 }
 
@@ -1425,17 +1710,21 @@ torch::Tensor wgrad_finish(torch::Tensor ws, c10::optional<torch::Tensor> acc,
 // auto's use of the row-order kernel on or off (off: P2PVG_WGRAD_ROWS=pertap)
 void set_wgrad_rows(bool on) { g_wgrad_rows = on; }
 bool wgrad_rows() { return g_wgrad_rows; }
+// the same for the 16-wide narrow kernel (off: P2PVG_WGRAD_NARROW=pertap)
+void set_wgrad_narrow(bool on) { g_wgrad_narrow = on; }
+bool wgrad_narrow() { return g_wgrad_narrow; }
 
 // Host only: the path conv2d_nhwc_wgrad takes for a 3x3 stride-1 PAD == 0
 // call over a zero-ringed X of A channels (A1 of them in the first source)
-// and a Y of B channels on an HO x WO map: "per_tap", "taps_strip" or
-// "taps_rows". The three give the same bits wherever auto picks among them,
-// so this is how a test sees the choice.
+// and a Y of B channels on an HO x WO map: "per_tap", "taps_strip",
+// "taps_rows" or "taps_narrow". They give the same bits wherever auto picks
+// among them, so this is how a test sees the choice.
 std::string conv2d_wgrad_path(long B, long A, long A1, long HO, long WO,
                               long yring, long taps) {
   switch (wgrad_k3_path((int)B, (int)A, (int)A1, (int)HO, (int)WO, (int)yring,
                         taps)) {
     case WG_ROWS: return "taps_rows";
+    case WG_NARROW: return "taps_narrow";
     case WG_STRIP: return "taps_strip";
     default: return "per_tap";
   }
@@ -1451,7 +1740,9 @@ std::string conv2d_wgrad_path(long B, long A, long A1, long HO, long WO,
 // takes it, 1 requires it (raises otherwise). taps: the same three values for
 // the single-pass all-taps 3x3 strip kernel; 2 requires the row-order
 // all-taps kernel (64-wide maps; 3 / 4 the same with 64x64 / 32x64 tiles
-// forced, where 2 picks the tile by CU fill).
+// forced, where 2 picks the tile by CU fill); 5 requires the narrow all-taps
+// kernel (16-wide maps; 6 / 7 the same with 64x64 / 128x64 tiles forced,
+// where 5 takes 128x64 when B is a multiple of 128).
 torch::Tensor conv2d_nhwc_wgrad(torch::Tensor Y, torch::Tensor X, long R,
                                 long S, long stride, long pad, long splitp,
                                 c10::optional<torch::Tensor> acc, long yring,
@@ -1501,7 +1792,7 @@ torch::Tensor conv2d_nhwc_wgrad(torch::Tensor Y, torch::Tensor X, long R,
   // chunks) or, on 64-wide maps, the row-order kernel (one-row chunks)
   const bool k3_ringed = !use_thin && R == 3 && S == 3 && stride == 1 &&
                          pad == 0 && H >= HO + 2 && W >= WO + 2;
-  TORCH_CHECK(taps >= -1 && taps <= 4, "wgrad: taps must be -1..4");
+  TORCH_CHECK(taps >= -1 && taps <= 7, "wgrad: taps must be -1..7");
   TORCH_CHECK(taps < 1 || k3_ringed,
               "wgrad: taps path required but the geometry is not eligible");
   const WgradPath path =
@@ -1558,6 +1849,42 @@ torch::Tensor conv2d_nhwc_wgrad(torch::Tensor Y, torch::Tensor X, long R,
     else WGRAD_RLAUNCH(64);
 #undef WGRAD_RLAUNCH
     return wgrad_finish(rws, acc, sp, B, A, E, rstream);
+  }
+
+  if (path == WG_NARROW) {
+    // per-tap slabs and combine; a chunk is the per-tap kernel's 64 pixels
+    // (four output rows), summed in its order: bitwise the per-tap result
+    int img_sh = 0;
+    while ((4 << img_sh) < HO) ++img_sh;  // chunks per image
+    auto nws = torch::empty({sp, B, 3, 3, A},
+                            Y.options().dtype(torch::kFloat32));
+    auto nstream = at::cuda::getCurrentCUDAStream();
+    const bool wide = taps == 7 || (taps != 6 && B % 128 == 0);
+    TORCH_CHECK(!wide || B % 128 == 0,
+                "wgrad: 128x64 narrow tiles need B a multiple of 128");
+#define WGRAD_NLAUNCH(BB)                                                     \
+  do {                                                                        \
+    static bool cfg = false;                                                  \
+    if (!cfg) {                                                               \
+      (void)hipFuncSetAttribute(                                              \
+          (const void*)&conv2d_wgrad_narrow_kernel<BB>,                       \
+          hipFuncAttributeMaxDynamicSharedMemorySize, NarrowCfg<BB>::LDS);    \
+      cfg = true;                                                             \
+    }                                                                         \
+    hipLaunchKernelGGL(                                                       \
+        (conv2d_wgrad_narrow_kernel<BB>), dim3((B / BB) * (A / 64), 1, sp),   \
+        dim3(NarrowCfg<BB>::NT), NarrowCfg<BB>::LDS, nstream,                 \
+        reinterpret_cast<const __bf16*>(Y.data_ptr()),                        \
+        reinterpret_cast<const __bf16*>(X.data_ptr()),                        \
+        X2.has_value() ? reinterpret_cast<const __bf16*>(X2->data_ptr())      \
+                       : nullptr,                                             \
+        nws.data_ptr<float>(), HO, B, H, W, A, A1, (int)yring,                \
+        p_total / PCH, p_per_slab / PCH, img_sh);                             \
+  } while (0)
+    if (wide) WGRAD_NLAUNCH(128);
+    else WGRAD_NLAUNCH(64);
+#undef WGRAD_NLAUNCH
+    return wgrad_finish(nws, acc, sp, B, A, E, nstream);
   }
 
   if (use_taps) {

@@ -88,6 +88,8 @@ std::string conv2d_wgrad_path(long B, long A, long A1, long HO, long WO,
                               long yring, long taps);
 void set_wgrad_rows(bool on);
 bool wgrad_rows();
+void set_wgrad_narrow(bool on);
+bool wgrad_narrow();
 std::vector<torch::Tensor> maxpool2x2_fwd(torch::Tensor in, long ri, long ro);
 torch::Tensor maxpool2x2_bwd(torch::Tensor gout, torch::Tensor idx, long H,
                              long W, long ri, long ro);
@@ -166,7 +168,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "acc: fp32 dense (B,R,S,A)-layout tensor to accumulate into; "
         "thin: -1 auto, 0 never, 1 require the thin-channel path; "
         "taps: the same for the single-pass all-taps 3x3 strip kernel, 2 "
-        "requires the row-order all-taps kernel (3 / 4: 64x64 / 32x64 tiles)",
+        "requires the row-order all-taps kernel (3 / 4: 64x64 / 32x64 "
+        "tiles), 5 the narrow all-taps kernel (16-wide maps; 6 / 7: 64x64 / "
+        "128x64 tiles)",
         pybind11::arg("Y"), pybind11::arg("X"), pybind11::arg("R"),
         pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"),
         pybind11::arg("splitp") = 0, pybind11::arg("acc") = c10::nullopt,
@@ -174,7 +178,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("thin") = -1, pybind11::arg("taps") = -1);
   m.def("conv2d_wgrad_path", &conv2d_wgrad_path,
         "host only: path of a 3x3 s1 pad-0 ringed-X wgrad call: 'per_tap', "
-        "'taps_strip' or 'taps_rows'",
+        "'taps_strip', 'taps_rows' or 'taps_narrow'",
         pybind11::arg("B"), pybind11::arg("A"), pybind11::arg("A1"),
         pybind11::arg("HO"), pybind11::arg("WO"), pybind11::arg("yring"),
         pybind11::arg("taps") = -1);
@@ -183,6 +187,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "false keeps those classes on the per-tap path (bitwise the same)",
         pybind11::arg("on"));
   m.def("wgrad_rows", &wgrad_rows, "current row-order wgrad auto mode");
+  m.def("set_wgrad_narrow", &set_wgrad_narrow,
+        "auto may use the narrow all-taps wgrad kernel on 16-wide maps "
+        "(default true); false keeps those classes on the per-tap path "
+        "(bitwise the same)",
+        pybind11::arg("on"));
+  m.def("wgrad_narrow", &wgrad_narrow, "current narrow wgrad auto mode");
   m.def("maxpool2x2_fwd", &maxpool2x2_fwd, "NHWC 2x2/s2 maxpool fwd (gfx950)",
         pybind11::arg("in"), pybind11::arg("ri") = 0, pybind11::arg("ro") = 0);
   m.def("maxpool2x2_bwd", &maxpool2x2_bwd, "NHWC 2x2/s2 maxpool bwd (gfx950)",

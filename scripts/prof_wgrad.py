@@ -1,18 +1,22 @@
 #!/usr/bin/env python
 """A/B the single-pass all-taps 3x3 wgrad kernels against the per-tap kernel.
 
-Run on a GPU box: python scripts/prof_wgrad.py [batch] [w64]
+Run on a GPU box: python scripts/prof_wgrad.py [batch] [w64|w16]
 For every vgg k3 wgrad shape (training form: X zero-ringed with pad=0, Y with
 a ring of 1; the decoder's concat layers as dual-X pairs) prints the pair time
 of the per-tap path (taps=0), of the strip all-taps kernel (taps=1) and of the
 row-order all-taps kernel with 64x64 and with 32x64 tiles (taps=3, taps=4;
-64-wide maps only), each where eligible. "Pair" is kernel plus combine: the
+64-wide maps only) and of the narrow all-taps kernel with 64x64 and with
+128x64 tiles (taps=6, taps=7; 16-wide maps only), each where eligible. "Pair" is kernel plus combine: the
 whole conv2d_nhwc_wgrad call, with the per-tap path's slabs in every column.
 Each time is the mean of REPS timings of 20 calls, followed by their max-min
 spread; "ratio" is per-tap over the fastest all-taps column, TF and staged
 TB/s are that column's. "bits" tells whether that column's result is bitwise
 the per-tap one. The argument w64 keeps only the 64-wide shapes, the two of
-the 64-pixel model and those the 128-pixel model adds.
+the 64-pixel model and those the 128-pixel model adds. The argument w16
+keeps the 16-wide shapes of the 64-pixel model, adds its 8-wide ones (per-tap
+only: what the other half of the <128,128> per-tap row costs) and the 16-wide
+ones of the 128-pixel model at a quarter of the batch.
 """
 import sys
 
@@ -26,7 +30,8 @@ CL = torch.channels_last
 ext = _hip_ext_loader.load()
 ARGS = sys.argv[1:]
 W64 = "w64" in ARGS
-ARGS = [a for a in ARGS if a != "w64"]
+W16 = "w16" in ARGS
+ARGS = [a for a in ARGS if a not in ("w64", "w16")]
 N = int(ARGS[0]) if ARGS else 128
 REPS = 3
 
@@ -52,8 +57,26 @@ SHAPES_128 = [
     ("v128 d4cat", (128, 128), 64, 128),
     ("v128 upc4.1", 128, 64, 64),
 ]
+# the 16- and 8-wide layers of the 64-pixel model that SHAPES lacks, and the
+# 16-wide classes of the 128-pixel model (fifth field: batch divisor)
+SHAPES_16 = [
+    ("vgg c3.0", 128, 16, 256),
+    ("vgg c3.x", 256, 16, 256),
+    ("vgg d3cat", (256, 256), 16, 256),
+    ("vgg upc3.2", 256, 16, 128),
+    ("vgg c4.0", 256, 8, 512),
+    ("vgg c4.x", 512, 8, 512),
+    ("vgg d2cat", (512, 512), 8, 512),
+    ("vgg upc2.2", 512, 8, 256),
+    ("v128 c4.0", 256, 16, 512, 4),
+    ("v128 c4.x", 512, 16, 512, 4),
+    ("v128 d3cat", (512, 512), 16, 512, 4),
+    ("v128 upc3.2", 512, 16, 256, 4),
+]
 if W64:
     SHAPES = [s for s in SHAPES if s[2] == 64] + SHAPES_128
+if W16:
+    SHAPES = SHAPES_16
 
 
 def timeit(f, n=20):
@@ -92,18 +115,20 @@ def cell(t):
     return f"{t[0]:>7.1f} ±{t[1]:<5.1f}" if t else f"{'-':>7} {'':<6}"
 
 
-MODES = [(1, "strip"), (3, "rows64"), (4, "rows32")]
+MODES = [(1, "strip"), (3, "rows64"), (4, "rows32"), (6, "nar64"),
+         (7, "nar128")]
 print(f"batch {N}")
-print(f"{'shape':<11} {'B':>4} {'A':>10} {'hw':>3} {'per-tap us':>14} "
+print(f"{'shape':<11} {'n':>4} {'B':>4} {'A':>10} {'hw':>3} {'per-tap us':>14} "
       + " ".join(f"{name + ' us':>14}" for _, name in MODES)
       + f" {'best':>6} {'ratio':>6} {'TF':>5} {'staged TB/s':>11} {'bits':>5} "
       f"{'err old':>9} {'err new':>9} {'scale':>8}")
-for tag, a_spec, h, b in SHAPES:
+for tag, a_spec, h, b, *div in SHAPES:
+    n = N // div[0] if div else N
     parts = a_spec if isinstance(a_spec, tuple) else (a_spec,)
     a = sum(parts)
     torch.manual_seed(0)
-    x = torch.randn(N, a, h, h, device="cuda").bfloat16()
-    g = torch.randn(N, b, h, h, device="cuda").bfloat16()
+    x = torch.randn(n, a, h, h, device="cuda").bfloat16()
+    g = torch.randn(n, b, h, h, device="cuda").bfloat16()
     ref = reference(x, g, b, a)
     scale = ref.abs().max().item()
     xs = [F.pad(p, (1,) * 4).contiguous(memory_format=CL)
@@ -130,10 +155,10 @@ for tag, a_spec, h, b in SHAPES:
             times[name] = None
             continue
         times[name] = timeit(lambda: call(taps))
-    flops = 2.0 * N * h * h * b * a * 9
+    flops = 2.0 * n * h * h * b * a * 9
     ybytes = gp.numel() * 2
     xbytes = sum(t.numel() for t in xs) * 2
-    head = (f"{tag:<11} {b:>4} {str(a_spec):>10} {h:>3} {cell(t_old)} "
+    head = (f"{tag:<11} {n:>4} {b:>4} {str(a_spec):>10} {h:>3} {cell(t_old)} "
             + " ".join(cell(times[name]) for _, name in MODES))
     if not outs:
         staged = 9 * (a // tile(a) * ybytes + b // tile(b) * xbytes)
@@ -144,8 +169,8 @@ for tag, a_spec, h, b in SHAPES:
     best = min(outs, key=lambda k: times[k][0])
     t_new = times[best][0]
     # every Y pixel once per a-tile, every X row as three shifted images
-    # once per b-tile (32-row b-tiles for rows32)
-    btile = 32 if best == "rows32" else 64
+    # once per b-tile (32-row b-tiles for rows32, 128-row ones for nar128)
+    btile = {"rows32": 32, "nar128": 128}.get(best, 64)
     staged = a // 64 * ybytes + b // btile * 3 * xbytes
     same = "same" if torch.equal(outs[best], w_old) else "differ"
     print(f"{head} {best:>6} {t_old[0] / t_new:>6.2f} "
