@@ -89,12 +89,13 @@ def _worker_seed_fn(rank: int):
     return _init
 
 
-def _make_loader(data, batch_size: int, cfg, rank: int = 0) -> DataLoader:
+def _make_loader(data, batch_size: int, cfg, rank: int = 0, sampler=None) -> DataLoader:
     pin = torch.cuda.is_available()
     return DataLoader(
         data,
         batch_size=batch_size,
-        shuffle=True,
+        shuffle=sampler is None,
+        sampler=sampler,
         drop_last=True,
         num_workers=getattr(cfg, "num_workers", 1),
         pin_memory=pin,
@@ -142,6 +143,27 @@ def get_h36m_generator(loader: DataLoader, device, dynamic_length: bool = True) 
                 pose_2d = pose_2d[:seq_len]
                 pose_3d = pose_3d[:seq_len]
             yield (pose_2d, pose_3d, camera_view)
+
+
+def get_h36m_test_generator(data, cfg, batch_size: int,
+                            dynamic_length: bool = False, rank: int = 0) -> Iterator:
+    """The h36m test generator at `batch_size` sequences per batch, for
+    evaluation. `get_data_generator(train=False)` keeps its fixed 10.
+
+    A batch larger than the split (the loader drops incomplete batches, so it
+    would never yield) draws sequences with replacement; every draw still
+    crops its own random window."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    if len(data) < 1:
+        raise ValueError("the h36m test split is empty")
+    device = torch.device(cfg.resolved_device() if hasattr(cfg, "resolved_device") else "cpu")
+    sampler = None
+    if batch_size > len(data):
+        sampler = torch.utils.data.RandomSampler(
+            data, replacement=True, num_samples=batch_size)
+    loader = _make_loader(data, batch_size, cfg, rank, sampler)
+    return get_h36m_generator(loader, device, dynamic_length)
 
 
 def get_device_mnist_generator(data, cfg, device, train: bool = True,

@@ -80,13 +80,17 @@ def reformat_data(raw_data: Dict) -> Dict:
     return data
 
 
-def standardize_dataset(data: Dict, scale: float = STD_SCALE) -> None:
+def standardize_dataset(data: Dict, scale: float = STD_SCALE):
     """Whole-dataset standardization to N(0, scale^2)
-    (reference align_and_normalize_dataset_v2, human36m.py:233-270)."""
+    (reference align_and_normalize_dataset_v2, human36m.py:233-270).
+
+    Returns the statistics it used, {"mean2", "std2", "mean3", "std3"}
+    (per-axis arrays), or None for an empty dataset: `std3 / scale` turns a
+    difference of standardized 3d poses back into the annotation's units."""
     p2, p3 = data["pose"]["2d"], data["pose"]["3d"]
     total = sum(s.shape[0] * s.shape[1] for s in p2)
     if total == 0:
-        return
+        return None
     mean2 = sum(s.sum(axis=(0, 1)) for s in p2) / total
     mean3 = sum(s.sum(axis=(0, 1)) for s in p3) / total
     std2 = np.sqrt(sum(((s - mean2) ** 2).sum(axis=(0, 1)) for s in p2) / total)
@@ -94,6 +98,7 @@ def standardize_dataset(data: Dict, scale: float = STD_SCALE) -> None:
     for i in range(len(p2)):
         p2[i] = scale * (p2[i] - mean2) / std2
         p3[i] = scale * (p3[i] - mean3) / std3
+    return {"mean2": mean2, "std2": std2, "mean3": mean3, "std3": std3}
 
 
 def _synthetic_sequences(n_seq: int, length: int, seed: int = 7):
@@ -133,6 +138,11 @@ class Human36mDataset(torch.utils.data.Dataset):
         self.train = train
         self.mode = mode
         self.skeleton = make_h36m_skeleton(remove_static_joints=False)
+        # a difference of 3d poses times pose_scale_3d is in pose_unit:
+        # "dataset" = the units of the annotation files, "standardized" = the
+        # N(0, STD_SCALE^2) space the model works in (synthetic fallback)
+        self.pose_scale_3d = np.ones(3, dtype=np.float32)
+        self.pose_unit = "standardized"
 
         have_h5 = True
         try:
@@ -157,7 +167,10 @@ class Human36mDataset(torch.utils.data.Dataset):
                 for i in range(len(self.data["pose"]["3d"])):
                     self.data["pose"]["3d"][i] = self.data["pose"]["3d"][i][:, kept]
                     self.data["pose"]["2d"][i] = self.data["pose"]["2d"][i][:, kept]
-            standardize_dataset(self.data)
+            stats = standardize_dataset(self.data)
+            if stats is not None:
+                self.pose_scale_3d = (stats["std3"] / STD_SCALE).astype(np.float32)
+                self.pose_unit = "dataset"
         else:
             if remove_static_joints:
                 self.skeleton = make_h36m_skeleton(True)

@@ -166,6 +166,20 @@ from .frame_metrics import frame_metrics, frame_metrics_backend  # noqa: E402
 from .clip_gather import clip_gather  # noqa: E402
 
 
+# ---------------------------------------------------------------------------
+# Pose scores for best-of-N skeleton evaluation (K20)
+# ---------------------------------------------------------------------------
+
+# gen (T,S,B,J,3), ref (T,B,J,3): pose_metrics -> (mpjpe, mse) (S,T,B) f32,
+# pose_spread -> mean pairwise sample distance (T,B) f32: HIP kernels on GPU,
+# torch ops on CPU. Bound at import for the reason given above.
+from .pose_metrics import (  # noqa: E402
+    pose_metrics,
+    pose_metrics_backend,
+    pose_spread,
+)
+
+
 __all__ = [
     "lstm_cell",
     "gaussian_kl",
@@ -173,6 +187,9 @@ __all__ = [
     "clip_gather",
     "frame_metrics",
     "frame_metrics_backend",
+    "pose_metrics",
+    "pose_spread",
+    "pose_metrics_backend",
     "backend_mode",
     "hip_available",
     "fused_adam_available",

@@ -105,6 +105,10 @@ torch::Tensor moving_mnist_render(torch::Tensor digits, torch::Tensor idx,
 std::vector<torch::Tensor> frame_metrics(torch::Tensor a, torch::Tensor b,
                                          torch::Tensor win, double data_range);
 torch::Tensor clip_gather(torch::Tensor bank, torch::Tensor idx, long L);
+std::vector<torch::Tensor> pose_metrics(torch::Tensor gen, torch::Tensor ref,
+                                        double w0, double w1, double w2);
+torch::Tensor pose_spread(torch::Tensor gen, double w0, double w1, double w2);
+long pose_spread_max_sj();
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
@@ -226,4 +230,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "idx (B) i32 host-validated -> (L,B,H,W,C) f32 = bank[idx, :L] / 255, "
         "correctly rounded",
         pybind11::arg("bank"), pybind11::arg("idx"), pybind11::arg("L"));
+  m.def("pose_metrics", &pose_metrics,
+        "per-frame MPJPE + MSE of S pose samples (gfx950, deterministic); gen "
+        "(T,S,B,J,3), ref (T,B,J,3) contiguous fp32/bf16/fp16, w = per-axis "
+        "scales -> (mpjpe (S,T,B) f32, mse (S,T,B) f32)",
+        pybind11::arg("gen"), pybind11::arg("ref"), pybind11::arg("w0"),
+        pybind11::arg("w1"), pybind11::arg("w2"));
+  m.def("pose_spread", &pose_spread,
+        "mean pairwise per-joint distance between the S samples of a frame "
+        "(gfx950, deterministic); gen (T,S,B,J,3) contiguous fp32/bf16/fp16, "
+        "S >= 2, S * J <= pose_spread_max_sj() -> (T,B) f32",
+        pybind11::arg("gen"), pybind11::arg("w0"), pybind11::arg("w1"),
+        pybind11::arg("w2"));
+  m.def("pose_spread_max_sj", &pose_spread_max_sj,
+        "host only: the largest S * J pose_spread stages in LDS");
 }
